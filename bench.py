@@ -8,14 +8,25 @@ One step = one pass of the fused Q6 pipeline over this GPU's lineitem shard
 row ranges (weak scaling); the only cross-GPU step is gathering the 16-byte
 partial revenues.
 
-    python bench.py [--gpus N --steps K --warmup W --sf 100]
+    python bench.py [--gpus N --steps K --warmup W --sf 100] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it generates the columns, runs
+the warm-up steps, times the K steps and prints the result line (`value`,
+`ms_per_step`, ...).  `--dump-outputs DIR` also writes what the last timed
+step returned, the exact 128-bit revenue, as DIR/revenue.npy (the value as
+one float64) and DIR/revenue_limbs32.npy (its four 32-bit limbs, low first,
+two's complement, each exactly representable in float64); the columns come
+from a counter-based generator with a fixed seed, so the same arguments give
+the same inputs in every run and every build.  Everything below that is not
+the headline -- the roofline pass, the other legs, the CPU baselines and the
+parity checks -- runs only with `--full` and extends the same line.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, this process starts N
 fresh rank processes of itself (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set,
 one GPU each) before it touches any GPU, waits for them and exits with the
 first failing rank's status; launched by torch.distributed.run it is one rank.
 
-Rank 0 prints one JSON line.  The `roofline` object prices the dominant kernel
+Rank 0 prints one JSON line.  With `--full`, the `roofline` object prices the dominant kernel
 (k_q6s, the predicate cascade: shipdate read whole, discount / quantity /
 extendedprice read only in the 128-B lines holding a row that passed the
 earlier predicates -- the lines the op-at-a-time plan's candidate lists touch)
@@ -60,6 +71,11 @@ def parse():
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--sf", type=float, default=100.0, help="scale factor per GPU")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline also run the roofline pass, the other legs, the CPU "
+                        "baselines and the parity checks (the --no-* options below trim these)")
     p.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     p.add_argument("--no-q1", action="store_true", help="skip the Q1 side measurement")
     p.add_argument("--no-parity", action="store_true", help="skip the full-size oracle checks")
@@ -78,7 +94,10 @@ def parse():
     p.add_argument("--leg-steps", type=int, default=3)
     p.add_argument("--dry-dist", action="store_true",
                    help="launch and check the ranks and the process group, then exit (no GPU work)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ---------------------------------------------------------------------------
@@ -243,6 +262,41 @@ def main():
     cx.barrier()
     elapsed = cx.max_over_ranks([time.perf_counter() - t])[0]
 
+    line = None
+    if rank == 0:
+        ms = elapsed / args.steps * 1e3
+        total_rows = rows * world
+        line = {
+            "metric": "Grows/sec + HBM GB/s vs peak, TPC-H SF100 Q1/Q6 columns at 1/2/4/8 GPUs",
+            "value": round(total_rows / (ms * 1e-3) / 1e9, 3),
+            "unit": "Grows/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms, 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "int64",
+            "data": "synthetic (TPC-H distributions, counter-based generator in HBM)",
+            "config": {"workload": "TPC-H Q6 fused column pipeline (select/select/thetaselect/"
+                                   "project/mul->hge/sum), lineitem SF%g per GPU" % args.sf,
+                       "rows_per_gpu": rows, "sf_per_gpu": args.sf,
+                       "parallelism": "row-range shards x%d" % world},
+            "dist_backend": args.dist_backend if world > 1 else None,
+            "world_size_seen": dist.get_world_size() if dist is not None else 1,
+            "revenue": str(revenue),
+            "gen_s": round(gen_s, 3),
+        }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, revenue)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
     # kernel time from HIP events around the fused Q6 (k_q6s) on the library stream
     gdk.prof_reset()
     gdk.prof_enable(True)
@@ -302,29 +356,9 @@ def main():
         parity["errors"] = perr
     ok = all(v is True for k, v in parity.items() if k != "errors") and not perr
     if rank == 0:
-        ms = elapsed / args.steps * 1e3
-        total_rows = rows * world
         achieved = q6_bytes / (kern_ms * 1e-3) / 1e9
         traffic, traffic_note = pmc_traffic(q6_kernel, rows)
-        line = {
-            "metric": "Grows/sec + HBM GB/s vs peak, TPC-H SF100 Q1/Q6 columns at 1/2/4/8 GPUs",
-            "value": round(total_rows / (ms * 1e-3) / 1e9, 3),
-            "unit": "Grows/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "int64",
-            "data": "synthetic (TPC-H distributions, counter-based generator in HBM)",
-            "config": {"workload": "TPC-H Q6 fused column pipeline (select/select/thetaselect/"
-                                   "project/mul->hge/sum), lineitem SF%g per GPU" % args.sf,
-                       "rows_per_gpu": rows, "sf_per_gpu": args.sf,
-                       "parallelism": "row-range shards x%d" % world},
-            "dist_backend": args.dist_backend if world > 1 else None,
-            "world_size_seen": dist.get_world_size() if dist is not None else 1,
+        line.update({
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                          "traffic": traffic, "traffic_source": traffic_note, "kernel": q6_kernel,
@@ -332,10 +366,8 @@ def main():
                          "bytes_per_launch": q6_bytes,
                          "bytes_full_read": rows * Q6_BYTES_PER_ROW},
             "cpu_baseline": cpu,
-            "revenue": str(revenue),
-            "gen_s": round(gen_s, 3),
             "parity": parity if not args.no_parity else None,
-        }
+        })
         line.update(extra)
         print(json.dumps(line), flush=True)
     if dist is not None:
@@ -344,8 +376,20 @@ def main():
         sys.exit(3)
 
 
+def dump_outputs(path, revenue):
+    """What a caller of the timed step receives, the exact revenue (a
+    128-bit integer), as .npy files: the value rounded to one float64, and
+    its four 32-bit limbs (low first, two's complement) as exact float64s."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    u = revenue & ((1 << 128) - 1)
+    np.save(os.path.join(path, "revenue.npy"), np.array([float(revenue)], np.float64))
+    np.save(os.path.join(path, "revenue_limbs32.npy"),
+            np.array([(u >> (32 * i)) & 0xFFFFFFFF for i in range(4)], np.float64))
+
+
 # ---------------------------------------------------------------------------
-# legs
+# legs (--full)
 # ---------------------------------------------------------------------------
 
 def _cpu_share():

@@ -100,7 +100,7 @@ smoke)
 	timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 	;;
 bench)
-	timeout -k 10 900 python bench.py > $O/bench.json 2> $O/bench.err
+	timeout -k 10 900 python bench.py --full > $O/bench.json 2> $O/bench.err
 	;;
 opbench)
 	timeout -k 10 600 python tools/opbench.py > $O/opbench.json 2> $O/opbench.err
@@ -158,11 +158,11 @@ final)
 	# round-end evidence: suite, smoke, bench, rocprof of the bench, PMC passes
 	timeout -k 10 1000 $T tests > $O/gpu_tests.log 2>&1
 	timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
-	timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err
+	timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err
 	cd /tmp && cd $GRAFT_REPO_ROOT
-	timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 bench.py --steps 10 --no-cpu > $O/prof_bench.json 2> $O/prof_bench.err
-	timeout -s KILL 180 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_f -o run -- python3 bench.py --no-dist-legs --no-op-legs --no-cpu --no-parity --steps 3 --warmup 1 > $O/pmc_f.log 2>&1
-	timeout -s KILL 180 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_w -o run -- python3 bench.py --no-dist-legs --no-op-legs --no-cpu --no-parity --steps 3 --warmup 1 > $O/pmc_w.log 2>&1
+	timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 bench.py --full --steps 10 --no-cpu > $O/prof_bench.json 2> $O/prof_bench.err
+	timeout -s KILL 180 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_f -o run -- python3 bench.py --full --no-dist-legs --no-op-legs --no-cpu --no-parity --steps 3 --warmup 1 > $O/pmc_f.log 2>&1
+	timeout -s KILL 180 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_w -o run -- python3 bench.py --full --no-dist-legs --no-op-legs --no-cpu --no-parity --steps 3 --warmup 1 > $O/pmc_w.log 2>&1
 	timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_jf -o run -- python3 tools/opbench.py --only config3 config4_group_sums > $O/pmc_jf.log 2>&1
 	timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_jw -o run -- python3 tools/opbench.py --only config3 config4_group_sums > $O/pmc_jw.log 2>&1
 	timeout -k 10 300 python tools/opbench.py > $O/opbench.json 2> $O/opbench.err
