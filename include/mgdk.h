@@ -71,12 +71,13 @@ typedef struct mgdk_bat {
 int mgdk_init(int device);                       /* select HIP device */
 /* Order-dependent floating-point folds (Welford moments, the running mean of
  * a flt/dbl average, a running flt/dbl SUM) are replayed in the reference's
- * order, bit for bit, one lane per group or partition.  A single group or
- * partition of at least `rows` rows (default 2^20; MGDK_BUN_NONE: never)
- * takes the parallel form instead -- blocked folds combined pairwise (Chan
- * et al. for the moments) -- whose results differ from the sequential ones
- * by rounding only, within the bounds DESIGN.md states (a few n ulp).
- * Process-wide; returns the previous value. */
+ * order, bit for bit, one lane per group or partition.  Every group or
+ * partition of at least `rows` candidate rows (default 2^20; MGDK_BUN_NONE:
+ * never), whatever the number of groups, takes the parallel form instead --
+ * blocked folds combined pairwise (Chan et al. for the moments) -- whose
+ * results differ from the sequential ones by rounding only, within the
+ * bounds DESIGN.md states (a few n ulp); the smaller groups of the same call
+ * stay bit-exact.  Process-wide; returns the previous value. */
 mgdk_BUN mgdk_set_fp_parallel_min(mgdk_BUN rows);
 const char *mgdk_GDKerrbuf(void);                /* gdk.h:1947 GDKerrbuf */
 void mgdk_GDKclrerr(void);

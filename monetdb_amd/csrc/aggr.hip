@@ -1735,12 +1735,18 @@ k_avg_keys(const oid *gids, oid gseq, oid gmin, BUN ngrp, BUN n, uint32_t *key, 
 template <typename T>
 __global__ void
 k_favg_replay(const T *vals, oid off, const uint32_t *perm, const uint64_t *start, const oid *gids, oid gseq,
-	      oid gmin, BUN ngrp, BUN n, bool skip_nils, double fac, double *out, long long *cnt)
+	      oid gmin, BUN ngrp, BUN n, bool skip_nils, double fac, double *out, long long *cnt, BUN par_min)
 {
 	const BUN k = (BUN) blockIdx.x * blockDim.x + threadIdx.x;
 	if (k >= ngrp)
 		return;
 	const BUN j0 = start ? start[k] : 0, j1 = start ? start[k + 1] : n;
+	// a large group among several is left to the parallel form (k_favg_seg):
+	// the count -1 tells the host, which reads the counts anyway, that there is one
+	if (start && fp_large(j1 - j0, par_min)) {
+		cnt[k] = -1;
+		return;
+	}
 	double a = 0;
 	long long c = 0;
 	bool nil = false;
@@ -1862,6 +1868,118 @@ k_favg_fin(const FAvg *part, unsigned nb, double fac, double *out, long long *cn
 	} else {
 		out[0] = fac != 1.0 ? s.a / fac : s.a;
 		cnt[0] = (long long) s.c;
+	}
+}
+
+// The same for the large groups among several (fp_large_segments): block t
+// folds tile t of the flat tile table -- lane l the positions l, l + 256, ...
+// of it, read through perm -- and one block per large group then merges that
+// group's tiles in tile order and writes the group's result.  A group's
+// tiles, lanes and merge order follow from its length alone.
+template <typename T>
+__global__ __launch_bounds__(256) void
+k_favg_seg(const T *vals, oid off, const uint32_t *perm, const FpTile *tiles, bool skip_nils, FAvg *part)
+{
+	__shared__ FAvg lds[256];
+	const FpTile t = tiles[blockIdx.x];
+	FAvg s{0, 0, 0};
+	long long c = 0;
+	for (BUN j = t.first + threadIdx.x; j < t.last; j += 256) {
+		const double x = (double) vals[off + perm[j]];
+		if (__builtin_isnan(x)) {
+			s.nil |= !skip_nils;
+			continue;
+		}
+		const double nn = (double) ++c;
+		if ((s.a > 0) == (x > 0))
+			s.a += (x - s.a) / nn;
+		else
+			s.a = s.a - s.a / nn + x / nn;
+	}
+	s.c = (double) c;
+	s = block_tree(s, [](const FAvg &x, const FAvg &y) { return favg_comb(x, y); }, lds);
+	if (threadIdx.x == 0)
+		part[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void
+k_favg_seg_fin(const FAvg *part, const FpSeg *segs, double fac, double *out, long long *cnt)
+{
+	__shared__ FAvg lds[256];
+	const FpSeg sg = segs[blockIdx.x];
+	const unsigned nb = sg.nb, per = (nb + 255) / 256, p0 = min(nb, threadIdx.x * per), p1 = min(nb, p0 + per);
+	FAvg s{0, 0, 0};
+	for (unsigned p = p0; p < p1; p++)
+		s = favg_comb(s, part[sg.tile0 + p]);
+	s = block_tree(s, [](const FAvg &x, const FAvg &y) { return favg_comb(x, y); }, lds);
+	if (threadIdx.x != 0)
+		return;
+	if (s.nil || s.c == 0) {
+		out[sg.id] = __builtin_nan("");
+		cnt[sg.id] = 0;
+	} else {
+		out[sg.id] = fac != 1.0 ? s.a / fac : s.a;
+		cnt[sg.id] = (long long) s.c;
+	}
+}
+
+// per segment: its tiles when it is large (0 otherwise) and whether it is
+__global__ __launch_bounds__(256) void
+k_fp_seg_count(const uint64_t *start, BUN nseg, BUN n, BUN thr, BUN fixed, uint32_t *nt, uint32_t *lg)
+{
+	for (BUN k = (BUN) blockIdx.x * blockDim.x + threadIdx.x; k < nseg; k += (BUN) gridDim.x * blockDim.x) {
+		const BUN len = start ? start[k + 1] - start[k] : n;
+		BUN tile;
+		const bool large = fp_large(len, thr);
+		nt[k] = large ? fp_tiling(len, &tile, fixed) : 0;
+		lg[k] = large;
+	}
+}
+
+// the large segments in segment order (loff: their ranks, toff: their first tiles)
+__global__ __launch_bounds__(256) void
+k_fp_seg_list(const uint64_t *start, BUN nseg, BUN n, BUN thr, BUN fixed, const uint64_t *toff,
+	      const uint64_t *loff, FpSeg *segs)
+{
+	for (BUN k = (BUN) blockIdx.x * blockDim.x + threadIdx.x; k < nseg; k += (BUN) gridDim.x * blockDim.x) {
+		const BUN first = start ? start[k] : 0, len = start ? start[k + 1] - first : n;
+		if (!fp_large(len, thr))
+			continue;
+		BUN tile;
+		FpSeg s;
+		s.id = k;
+		s.first = first;
+		s.len = len;
+		s.tile0 = toff[k];
+		s.nb = fp_tiling(len, &tile, fixed);
+		s.pad = 0;
+		segs[loff[k]] = s;
+	}
+}
+
+// the flat tile table: tile t belongs to the last large segment whose first
+// tile is at or before t
+__global__ __launch_bounds__(256) void
+k_fp_seg_tiles(const FpSeg *segs, BUN nlarge, BUN ntile, BUN fixed, FpTile *tiles)
+{
+	for (BUN t = (BUN) blockIdx.x * blockDim.x + threadIdx.x; t < ntile; t += (BUN) gridDim.x * blockDim.x) {
+		BUN lo = 0, hi = nlarge;
+		while (hi - lo > 1) {
+			const BUN mid = (lo + hi) / 2;
+			if (segs[mid].tile0 <= t)
+				lo = mid;
+			else
+				hi = mid;
+		}
+		const FpSeg s = segs[lo];
+		BUN tile;
+		(void) fp_tiling(s.len, &tile, fixed);
+		FpTile o;
+		o.seg = (uint32_t) lo;
+		o.tix = (uint32_t) (t - s.tile0);
+		o.first = s.first + (BUN) o.tix * tile;
+		o.last = min(s.first + s.len, o.first + tile);
+		tiles[t] = o;
 	}
 }
 
@@ -2065,6 +2183,49 @@ group_rows(const AggrInit &a, GroupRows &gr)
 	return 0;
 }
 
+int
+fp_large_segments(const uint64_t *start, BUN nseg, BUN n, BUN thr, FpSegs &ls, BUN fixed_tile)
+{
+	ls.nseg = ls.ntile = 0;
+	if (n == 0 || n < thr || nseg == 0)
+		return 0;
+	if (nseg >= 0xffffffffull) {
+		seterr("42000!more than 2^32-1 segments on the device path\n");
+		return -1;
+	}
+	hipStream_t st = stream();
+	DevBuf nt(nseg * 4), lg(nseg * 4);
+	ls.toff = (uint64_t *) dalloc(nseg * 8);
+	ls.loff = (uint64_t *) dalloc(nseg * 8);
+	if (!nt.p || !lg.p || !ls.toff || !ls.loff)
+		return -1;
+	const dim3 grid(grid_for(nseg, 1024, 8192)), blk(256);
+	hipLaunchKernelGGL(k_fp_seg_count, grid, blk, 0, st, start, nseg, n, thr, fixed_tile, nt.as<uint32_t>(),
+			   lg.as<uint32_t>());
+	uint64_t ntile = 0, nlarge = 0;
+	if (exclusive_scan(nt.as<uint32_t>(), ls.toff, nseg, &ntile) != 0)
+		return -1;
+	if (ntile == 0)
+		return 0;
+	if (exclusive_scan(lg.as<uint32_t>(), ls.loff, nseg, &nlarge) != 0)
+		return -1;
+	if (ntile >= 0x7fffffffull) {
+		seterr("42000!too many tiles on the device path\n");
+		return -1;
+	}
+	ls.segs = (FpSeg *) dalloc(nlarge * sizeof(FpSeg));
+	ls.tiles = (FpTile *) dalloc(ntile * sizeof(FpTile));
+	if (!ls.segs || !ls.tiles)
+		return -1;
+	hipLaunchKernelGGL(k_fp_seg_list, grid, blk, 0, st, start, nseg, n, thr, fixed_tile, ls.toff, ls.loff,
+			   ls.segs);
+	hipLaunchKernelGGL(k_fp_seg_tiles, dim3(grid_for(ntile, 256, 8192)), blk, 0, st, ls.segs, (BUN) nlarge,
+			   (BUN) ntile, fixed_tile, ls.tiles);
+	ls.nseg = nlarge;
+	ls.ntile = ntile;
+	return 0;
+}
+
 mgdk_bat *
 cand_values_at(mgdk_bat *b, const Cand &ci)
 {
@@ -2264,12 +2425,12 @@ mgdk_BATcalcavg(mgdk_bat *b, mgdk_bat *s, double *avg, mgdk_BUN *vals, int scale
 				hipLaunchKernelGGL((k_favg_replay<float>), dim3(1), dim3(64), 0, st, (const float *) v->theap, off,
 						   (const uint32_t *) nullptr, (const uint64_t *) nullptr, (const oid *) nullptr,
 						   (oid) MGDK_OID_NIL, (oid) 0, (BUN) 1, ci.n, true, 1.0, out.as<double>(),
-						   cnt.as<long long>());
+						   cnt.as<long long>(), (BUN) MGDK_BUN_NONE);
 			else
 				hipLaunchKernelGGL((k_favg_replay<double>), dim3(1), dim3(64), 0, st, (const double *) v->theap, off,
 						   (const uint32_t *) nullptr, (const uint64_t *) nullptr, (const oid *) nullptr,
 						   (oid) MGDK_OID_NIL, (oid) 0, (BUN) 1, ci.n, true, 1.0, out.as<double>(),
-						   cnt.as<long long>());
+						   cnt.as<long long>(), (BUN) MGDK_BUN_NONE);
 			ok = sync();
 		}
 		double *h = (double *) pinned(16);
@@ -2434,6 +2595,7 @@ mgdk_BATgroupavg(mgdk_bat **bnp, mgdk_bat **cntsp, mgdk_bat *b, mgdk_bat *g, mgd
 		bool ok = group_rows(a, gr) == 0;
 		const uint32_t *perm = gr.perm;
 		const uint64_t *sp = gr.start_p;
+		BUN seg_min = MGDK_BUN_NONE;
 		if (ok && ng == 1 && a.ci.n >= fp_parallel_min()) {
 			unsigned nb = (unsigned) min((BUN) 2048, (a.ci.n + 4095) / 4096);
 			const BUN tile = (a.ci.n + nb - 1) / nb;
@@ -2452,16 +2614,20 @@ mgdk_BATgroupavg(mgdk_bat **bnp, mgdk_bat **cntsp, mgdk_bat *b, mgdk_bat *g, mgd
 				ok = sync();
 			}
 		} else if (ok) {
+			// the replay leaves the groups of at least fp_parallel_min() rows
+			// among several to the parallel form below
+			const BUN par_min = ng >= 2 && a.ci.n >= fp_parallel_min() ? fp_parallel_min() : (BUN) MGDK_BUN_NONE;
 			const dim3 grid((unsigned) ((ng + 63) / 64)), blk(64);
 			if (bt == MGDK_flt)
 				hipLaunchKernelGGL((k_favg_replay<float>), grid, blk, 0, st, (const float *) b->theap, off, perm,
 						   sp, a.gids, a.gseq, a.min, ng, a.ci.n, skip_nils, fac, (double *) bn->theap,
-						   (long long *) cn->theap);
+						   (long long *) cn->theap, par_min);
 			else
 				hipLaunchKernelGGL((k_favg_replay<double>), grid, blk, 0, st, (const double *) b->theap, off,
 						   perm, sp, a.gids, a.gseq, a.min, ng, a.ci.n, skip_nils, fac,
-						   (double *) bn->theap, (long long *) cn->theap);
+						   (double *) bn->theap, (long long *) cn->theap, par_min);
 			ok = sync();
+			seg_min = par_min;
 		}
 		if (!ok) {
 			mgdk_BBPunfix(bn);
@@ -2475,8 +2641,39 @@ mgdk_BATgroupavg(mgdk_bat **bnp, mgdk_bat **cntsp, mgdk_bat *b, mgdk_bat *g, mgd
 			mgdk_BBPunfix(cn);
 			return -1;
 		}
-		for (BUN k = 0; k < ng; k++)
+		long long signs = 0;     // a count of -1: a group left to the parallel form
+		for (BUN k = 0; k < ng; k++) {
 			nils |= hc[k] == 0;
+			signs |= hc[k];
+		}
+		if (signs < 0) {
+			// the groups the replay left out: one grid over the flat tile
+			// table of all of them, one block per group to merge its tiles
+			ProfScope pseg("groupavg_fp_seg");
+			FpSegs ls;
+			ok = fp_large_segments(sp, ng, a.ci.n, seg_min, ls) == 0 && ls.nseg > 0;
+			DevBuf part((size_t) ls.ntile * sizeof(FAvg));
+			ok = ok && part.p != nullptr;
+			if (ok) {
+				const dim3 tg((unsigned) ls.ntile), tb(256);
+				if (bt == MGDK_flt)
+					hipLaunchKernelGGL((k_favg_seg<float>), tg, tb, 0, st, (const float *) b->theap, off, perm, ls.tiles,
+							   skip_nils, part.as<FAvg>());
+				else
+					hipLaunchKernelGGL((k_favg_seg<double>), tg, tb, 0, st, (const double *) b->theap, off, perm,
+							   ls.tiles, skip_nils, part.as<FAvg>());
+				hipLaunchKernelGGL(k_favg_seg_fin, dim3((unsigned) ls.nseg), tb, 0, st, part.as<FAvg>(), ls.segs, fac,
+						   (double *) bn->theap, (long long *) cn->theap);
+				ok = sync() && hip_ok(hipMemcpy(hc.data(), cn->theap, ng * 8, hipMemcpyDeviceToHost), "memcpy");
+			}
+			if (!ok) {
+				mgdk_BBPunfix(bn);
+				mgdk_BBPunfix(cn);
+				return -1;
+			}
+			for (BUN k = 0; k < ng; k++)
+				nils |= hc[k] == 0;
+		}
 	} else {
 		// AVERAGE_ITER's invariant: avg * n + rem == sum, 0 <= rem < n
 		bn = newbat(hb, MGDK_dbl, ng);

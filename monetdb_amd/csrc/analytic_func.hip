@@ -1214,11 +1214,15 @@ struct FSum {
 
 template <typename T1, typename T2>
 __global__ __launch_bounds__(64) void
-k_fsum_replay(const T1 *b, Starts part, const int8_t *o, bool forward, T2 *out, uint32_t *flags)
+k_fsum_replay(const T1 *b, Starts part, const int8_t *o, bool forward, T2 *out, uint32_t *flags, BUN par_min)
 {
 	const BUN k = (BUN) blockIdx.x * blockDim.x + threadIdx.x;
 	uint32_t fl = 0;
-	if (k < part.m) {
+	// a large partition among several is left to the parallel form
+	// (k_rs_*_seg): flag bit 3 tells the host that there is one
+	if (k < part.m && fp_large(part.end_of(k) - part.at(k), par_min)) {
+		fl = 8;
+	} else if (k < part.m) {
 		const BUN ps = part.at(k), pe = part.end_of(k);
 		FSum<T2> cur;
 		cur.zero();
@@ -1447,9 +1451,10 @@ struct RsStage {
 
 template <typename T1, typename T2>
 __device__ __forceinline__ void
-rs_load(const T1 *b, const int8_t *o, BUN n, bool fwd, RsStage<T1> &sg, FSum<T2> (&x)[RS_PER], bool (&e)[RS_PER])
+rs_load(const T1 *b, const int8_t *o, BUN n, bool fwd, BUN tb, RsStage<T1> &sg, FSum<T2> (&x)[RS_PER],
+	bool (&e)[RS_PER])
 {
-	const BUN t0 = (BUN) blockIdx.x * RS_TILE;
+	const BUN t0 = tb * RS_TILE;
 #pragma unroll
 	for (unsigned k = 0; k < RS_PER; k++) {
 		const unsigned i = k * 256 + threadIdx.x;
@@ -1524,17 +1529,20 @@ rs_block_excl(FSum<T2> v, FSum<T2> *wt, uint32_t &fl, FSum<T2> *total)
 	return rs_comb(wp, ex, fl);
 }
 
+// (tb: the tile's index within its partition, slot: its place in tot / fend;
+// the same number with one partition)
 template <typename T1, typename T2>
-__global__ __launch_bounds__(256) void
-k_rs_tile(const T1 *b, const int8_t *o, BUN n, bool fwd, FSum<T2> *tot, BUN *fend, uint32_t *flags)
+__device__ __forceinline__ void
+rs_tile_body(const T1 *b, const int8_t *o, BUN n, bool fwd, BUN tb, BUN slot, FSum<T2> *tot, BUN *fend,
+	     uint32_t *flags)
 {
 	__shared__ FSum<T2> lds[256];
 	__shared__ BUN sm[256];
 	__shared__ RsStage<T1> sg;
-	const BUN q0 = (BUN) blockIdx.x * RS_TILE + threadIdx.x * RS_PER;
+	const BUN q0 = tb * RS_TILE + threadIdx.x * RS_PER;
 	FSum<T2> x[RS_PER];
 	bool e[RS_PER];
-	rs_load<T1, T2>(b, o, n, fwd, sg, x, e);
+	rs_load<T1, T2>(b, o, n, fwd, tb, sg, x, e);
 	FSum<T2> acc;
 	acc.zero();
 	BUN fe = ~(BUN) 0;
@@ -1556,11 +1564,31 @@ k_rs_tile(const T1 *b, const int8_t *o, BUN n, bool fwd, FSum<T2> *tot, BUN *fen
 	__syncthreads();
 	fe = min(min(sm[0], sm[1]), min(sm[2], sm[3]));
 	if (threadIdx.x == 0) {
-		tot[blockIdx.x] = total;
-		fend[blockIdx.x] = fe;
+		tot[slot] = total;
+		fend[slot] = fe;
 	}
 	if (fl)
 		atomicOr(flags, fl);
+}
+
+template <typename T1, typename T2>
+__global__ __launch_bounds__(256) void
+k_rs_tile(const T1 *b, const int8_t *o, BUN n, bool fwd, FSum<T2> *tot, BUN *fend, uint32_t *flags)
+{
+	rs_tile_body<T1, T2>(b, o, n, fwd, blockIdx.x, blockIdx.x, tot, fend, flags);
+}
+
+// the same over the flat tile table of the large partitions: a tile's
+// positions are counted within its partition (frame 4 backwards within it),
+// whose first row (frame 4) or last row (frame 3) ends a run
+template <typename T1, typename T2>
+__global__ __launch_bounds__(256) void
+k_rs_tile_seg(const T1 *b, const int8_t *o, bool fwd, const FpSeg *segs, const FpTile *tiles, FSum<T2> *tot,
+	      BUN *fend, uint32_t *flags)
+{
+	const FpTile t = tiles[blockIdx.x];
+	const FpSeg sg = segs[t.seg];
+	rs_tile_body<T1, T2>(b + sg.first, o + sg.first, sg.len, fwd, t.tix, blockIdx.x, tot, fend, flags);
 }
 
 // pre[t] = the fold of the tiles before t (in order); nxt[t] = the first run
@@ -1571,8 +1599,8 @@ k_rs_tile(const T1 *b, const int8_t *o, BUN n, bool fwd, FSum<T2> *tot, BUN *fen
 constexpr unsigned RS_TPT = 32;     // tiles per thread per round (all loaded at once)
 
 template <typename T2>
-__global__ __launch_bounds__(1024) void
-k_rs_tiles(const FSum<T2> *tot, const BUN *fend, BUN nt, FSum<T2> *pre, BUN *nxt, uint32_t *flags)
+__device__ __forceinline__ void
+rs_tiles_body(const FSum<T2> *tot, const BUN *fend, BUN nt, FSum<T2> *pre, BUN *nxt, uint32_t *flags)
 {
 	__shared__ FSum<T2> wt[16];
 	__shared__ BUN wm[16];
@@ -1652,27 +1680,43 @@ k_rs_tiles(const FSum<T2> *tot, const BUN *fend, BUN nt, FSum<T2> *pre, BUN *nxt
 		atomicOr(flags, fl);
 }
 
+template <typename T2>
+__global__ __launch_bounds__(1024) void
+k_rs_tiles(const FSum<T2> *tot, const BUN *fend, BUN nt, FSum<T2> *pre, BUN *nxt, uint32_t *flags)
+{
+	rs_tiles_body<T2>(tot, fend, nt, pre, nxt, flags);
+}
+
+// one workgroup per large partition: the scan restarts at its first tile
+template <typename T2>
+__global__ __launch_bounds__(1024) void
+k_rs_tiles_seg(const FpSeg *segs, const FSum<T2> *tot, const BUN *fend, FSum<T2> *pre, BUN *nxt, uint32_t *flags)
+{
+	const FpSeg sg = segs[blockIdx.x];
+	rs_tiles_body<T2>(tot + sg.tile0, fend + sg.tile0, sg.nb, pre + sg.tile0, nxt + sg.tile0, flags);
+}
+
 // pass 3: every position's value -- the running sum at the end of its peer
 // run when that end lies inside the tile (read back from LDS), else its own
 // running sum for now -- stored row-wise; pass 4 gives the positions of the
 // tile's open last run (its end in a later tile) that end's value, read
 // from the output in place (end positions are never rewritten)
 template <typename T1, typename T2>
-__global__ __launch_bounds__(256) void
-k_rs_write(const T1 *b, const int8_t *o, BUN n, bool fwd, const FSum<T2> *pre, const BUN *nxt, int pass, T2 *out,
-	   uint32_t *flags)
+__device__ __forceinline__ void
+rs_write_body(const T1 *b, const int8_t *o, BUN n, bool fwd, BUN tb, BUN slot, const FSum<T2> *pre, const BUN *nxt,
+	      int pass, T2 *out, uint32_t *flags)
 {
 	__shared__ FSum<T2> ls[256];
 	__shared__ BUN lm[256];
 	__shared__ RsStage<T1> sg;
 	__shared__ T2 wo[RS_TILE + RS_TILE / RS_PER];
-	const BUN t0 = (BUN) blockIdx.x * RS_TILE;
+	const BUN t0 = tb * RS_TILE;
 	const BUN q0 = t0 + threadIdx.x * RS_PER;
 	const BUN tend = t0 + RS_TILE < n ? t0 + RS_TILE : n;
 	uint32_t fl = 0;
 	FSum<T2> x[RS_PER];
 	bool e[RS_PER];
-	rs_load<T1, T2>(b, o, n, fwd, sg, x, e);
+	rs_load<T1, T2>(b, o, n, fwd, tb, sg, x, e);
 	// the first run end at or after each lane's chunk, inside the tile
 	BUN fe = ~(BUN) 0;
 #pragma unroll
@@ -1692,7 +1736,7 @@ k_rs_write(const T1 *b, const int8_t *o, BUN n, bool fwd, const FSum<T2> *pre, c
 	const BUN after = threadIdx.x + 1 < 256 ? lm[threadIdx.x + 1] : ~(BUN) 0;
 	if (pass == 1) {
 		// the open last run: positions whose end is in a later tile
-		BUN endq = after != ~(BUN) 0 ? after : nxt[blockIdx.x];
+		BUN endq = after != ~(BUN) 0 ? after : nxt[slot];
 		if (after != ~(BUN) 0)
 			return;      // this lane's positions all end inside the tile
 #pragma unroll
@@ -1713,7 +1757,7 @@ k_rs_write(const T1 *b, const int8_t *o, BUN n, bool fwd, const FSum<T2> *pre, c
 		acc = rs_comb(acc, x[k], fl);
 	FSum<T2> total;
 	const FSum<T2> ex = rs_block_excl(acc, ls, fl, &total);
-	FSum<T2> run = rs_comb(pre[blockIdx.x], ex, fl);
+	FSum<T2> run = rs_comb(pre[slot], ex, fl);
 	const unsigned l0 = threadIdx.x * RS_PER;
 #pragma unroll
 	for (unsigned k = 0; k < RS_PER; k++) {
@@ -1751,6 +1795,33 @@ k_rs_write(const T1 *b, const int8_t *o, BUN n, bool fwd, const FSum<T2> *pre, c
 }
 
 template <typename T1, typename T2>
+__global__ __launch_bounds__(256) void
+k_rs_write(const T1 *b, const int8_t *o, BUN n, bool fwd, const FSum<T2> *pre, const BUN *nxt, int pass, T2 *out,
+	   uint32_t *flags)
+{
+	rs_write_body<T1, T2>(b, o, n, fwd, blockIdx.x, blockIdx.x, pre, nxt, pass, out, flags);
+}
+
+template <typename T1, typename T2>
+__global__ __launch_bounds__(256) void
+k_rs_write_seg(const T1 *b, const int8_t *o, bool fwd, const FpSeg *segs, const FpTile *tiles, const FSum<T2> *pre,
+	       const BUN *nxt, int pass, T2 *out, uint32_t *flags)
+{
+	const FpTile t = tiles[blockIdx.x];
+	const FpSeg sg = segs[t.seg];
+	rs_write_body<T1, T2>(b + sg.first, o + sg.first, sg.len, fwd, t.tix, blockIdx.x, pre, nxt, pass,
+			      out + sg.first, flags);
+}
+
+// the partitions' offsets (m + 1 of them) for fp_large_segments
+__global__ __launch_bounds__(256) void
+k_part_offsets(Starts part, uint64_t *off)
+{
+	for (BUN k = (BUN) blockIdx.x * blockDim.x + threadIdx.x; k <= part.m; k += (BUN) gridDim.x * blockDim.x)
+		off[k] = k < part.m ? part.at(k) : part.n;
+}
+
+template <typename T1, typename T2>
 int
 run_fsum_par(const T1 *bv, const int8_t *o, BUN n, bool fwd, T2 *out, uint32_t *flags)
 {
@@ -1774,6 +1845,41 @@ run_fsum_par(const T1 *bv, const int8_t *o, BUN n, bool fwd, T2 *out, uint32_t *
 	return sync() ? 0 : -1;
 }
 
+// frames 3 / 4 over several partitions: the ones of at least par_min rows,
+// which the replay left out, in the parallel form -- the four passes over
+// the flat tile table of RS_TILE-position tiles that never straddle a
+// partition start
+template <typename T1, typename T2>
+int
+run_fsum_large(const T1 *bv, const Starts &part, const int8_t *o, BUN n, BUN par_min, bool fwd, T2 *out,
+	       uint32_t *flags)
+{
+	hipStream_t st = stream();
+	ProfScope pseg("analyticalsum_fp_seg");
+	FpSegs ls;
+	DevBuf off((part.m + 1) * 8);
+	if (!off.p)
+		return -1;
+	hipLaunchKernelGGL(k_part_offsets, dim3(grid_for(part.m + 1, 1024, 1024)), dim3(256), 0, st, part,
+			   off.as<uint64_t>());
+	if (fp_large_segments(off.as<uint64_t>(), part.m, n, par_min, ls, RS_TILE) != 0 || ls.nseg == 0)
+		return -1;
+	const BUN nt = ls.ntile;
+	DevBuf tot(nt * sizeof(FSum<T2>)), pre(nt * sizeof(FSum<T2>)), fend(nt * sizeof(BUN)), nxt(nt * sizeof(BUN));
+	if (!tot.p || !pre.p || !fend.p || !nxt.p)
+		return -1;
+	const dim3 tg((unsigned) nt), tb(256);
+	hipLaunchKernelGGL((k_rs_tile_seg<T1, T2>), tg, tb, 0, st, bv, o, fwd, ls.segs, ls.tiles, tot.as<FSum<T2>>(),
+			   fend.as<BUN>(), flags);
+	hipLaunchKernelGGL((k_rs_tiles_seg<T2>), dim3((unsigned) ls.nseg), dim3(1024), 0, st, ls.segs, tot.as<FSum<T2>>(),
+			   fend.as<BUN>(), pre.as<FSum<T2>>(), nxt.as<BUN>(), flags);
+	hipLaunchKernelGGL((k_rs_write_seg<T1, T2>), tg, tb, 0, st, bv, o, fwd, ls.segs, ls.tiles, pre.as<FSum<T2>>(),
+			   nxt.as<BUN>(), 0, out, flags);
+	hipLaunchKernelGGL((k_rs_write_seg<T1, T2>), tg, tb, 0, st, bv, o, fwd, ls.segs, ls.tiles, pre.as<FSum<T2>>(),
+			   nxt.as<BUN>(), 1, out, flags);
+	return sync() ? 0 : -1;
+}
+
 template <typename T1, typename T2>
 int
 run_fsum(mgdk_bat *r, mgdk_bat *p, mgdk_bat *o, mgdk_bat *b, mgdk_bat *s, mgdk_bat *e, int frame_type)
@@ -1788,19 +1894,23 @@ run_fsum(mgdk_bat *r, mgdk_bat *p, mgdk_bat *o, mgdk_bat *b, mgdk_bat *s, mgdk_b
 		return -1;
 	mgdk_bat *Sp = nullptr;
 	int rc = -1;
+	Starts part{};
+	BUN par_min = MGDK_BUN_NONE;
 	if (frame_type == 6) {
 		hipLaunchKernelGGL((k_fsum_row<T1, T2>), dim3(grid_for(n, 1024, 8192)), dim3(256), 0, st, bv, n, out,
 				   fl.as<uint32_t>());
 	} else {
-		Starts part;
 		if (make_starts(p ? (const int8_t *) p->theap : nullptr, n, part, &Sp) < 0)
 			goto out;
 		if ((frame_type == 3 || frame_type == 4) && part.m == 1 && n >= fp_parallel_min()) {
 			if (run_fsum_par<T1, T2>(bv, (const int8_t *) o->theap, n, frame_type == 3, out, fl.as<uint32_t>()) < 0)
 				goto out;
 		} else if (frame_type == 3 || frame_type == 4) {
+			// (the partitions of at least fp_parallel_min() rows are left to
+			// run_fsum_large below)
+			par_min = n >= fp_parallel_min() ? fp_parallel_min() : (BUN) MGDK_BUN_NONE;
 			hipLaunchKernelGGL((k_fsum_replay<T1, T2>), dim3((unsigned) ((part.m + 63) / 64)), dim3(64), 0, st, bv, part,
-					   (const int8_t *) o->theap, frame_type == 3, out, fl.as<uint32_t>());
+					   (const int8_t *) o->theap, frame_type == 3, out, fl.as<uint32_t>(), par_min);
 		} else {
 			if (n >= 0xffffffffull) {
 				seterr("42000!GDKanalyticalsum: more than 2^32-1 rows on the device path\n");
@@ -1876,6 +1986,13 @@ run_fsum(mgdk_bat *r, mgdk_bat *p, mgdk_bat *o, mgdk_bat *b, mgdk_bat *s, mgdk_b
 		uint32_t *h = (uint32_t *) pinned(16);
 		if (!hip_ok(hipMemcpyAsync(h, fl.p, 4, hipMemcpyDeviceToHost, st), "memcpy") || !sync())
 			goto out;
+		if (h[0] & 8) {
+			// the replay of frames 3 / 4 left large partitions out
+			if (run_fsum_large<T1, T2>(bv, part, (const int8_t *) o->theap, n, par_min, frame_type == 3, out,
+						   fl.as<uint32_t>()) < 0 ||
+			    !hip_ok(hipMemcpyAsync(h, fl.p, 4, hipMemcpyDeviceToHost, st), "memcpy") || !sync())
+				goto out;
+		}
 		if (h[0] & 4) {
 			seterr("22003!overflow in sum aggregate.\n42000!error while calculating floating-point sum\n");
 			goto out;

@@ -16,8 +16,10 @@
 // group's recurrence -- all groups at once -- with the reference's operations
 // in the reference's order and no contraction into fused multiply-adds (the
 // pragma below), so the results are the reference's bit for bit.  A group is
-// a chain of dependent divisions: the device wins with many groups; a single
-// group (the BATcalc* forms) runs at one lane's speed.
+// a chain of dependent divisions: the device wins with many groups.  A
+// whole column (the BATcalc* forms) and every group of at least
+// fp_parallel_min() rows take the parallel form further down instead,
+// within the bounds DESIGN.md 11.5 states.
 //
 // The quantiles follow the reference's plan: sort g, sub-sort b within the
 // groups (mgdk_BATsort, both on the device); one lane per run of equal group
@@ -50,7 +52,8 @@ enum { ST_VAR = 0, ST_COV = 1, ST_COR = 2 };
 constexpr unsigned long long CNT_NONE = ~0ull;
 
 // flags: bit 0 overflow ("22003!overflow in calculation."), bit 1 a nil result
-// the reference counts (nils / nils2 of dogroupstdev and its kin)
+// the reference counts (nils / nils2 of dogroupstdev and its kin), bit 2 a
+// group was left to the parallel form (par_min)
 struct MomArgs {
 	oid off;               // position of candidate 0 in the value columns
 	const uint32_t *perm;  // group_rows: NULL identity
@@ -59,6 +62,7 @@ struct MomArgs {
 	oid gseq, gmin;
 	BUN ngrp, n;
 	bool all;              // whole column (BATcalc*): every row, nils skipped
+	BUN par_min;           // groups of at least so many rows are left to the parallel form (k_mom_seg)
 	bool skip_nils, issample, variance;
 	double *res;
 	double *avg;           // BATcalc{stdev,variance}: the mean (or NULL)
@@ -77,6 +81,10 @@ k_moments(const T *v1, const T *v2, MomArgs a)
 	if (k >= a.ngrp)
 		return;
 	const BUN j0 = a.start ? a.start[k] : 0, j1 = a.start ? a.start[k + 1] : a.n;
+	if (fp_large(j1 - j0, a.par_min)) {
+		atomicOr(a.flags, 4u);
+		return;
+	}
 	unsigned long long cnt = 0;
 	double mean1 = 0, mean2 = 0, m2 = 0, up = 0, down1 = 0, down2 = 0;
 	bool ovf = false;
@@ -268,6 +276,9 @@ const_dbl(oid hseq, double v, BUN n)
 	return mgdk_BATconstant(hseq, MGDK_dbl, &v, n);
 }
 
+// the large groups of a grouped call in the parallel form (below)
+int seg_moments(int kind, int tt, const void *v1, const void *v2, const MomArgs &m, const FpSegs &ls, void **part);
+
 // dogroupstdev / dogroupcovariance / BATgroupcorrelation
 mgdk_bat *
 group_moments(const char *fn, int kind, mgdk_bat *b1, mgdk_bat *b2, mgdk_bat *g, mgdk_bat *e, mgdk_bat *s,
@@ -365,6 +376,7 @@ group_moments(const char *fn, int kind, mgdk_bat *b1, mgdk_bat *b2, mgdk_bat *g,
 	m.ngrp = ng;
 	m.n = a.ci.n;
 	m.all = false;
+	m.par_min = MGDK_BUN_NONE;
 	m.skip_nils = skip_nils;
 	m.issample = issample;
 	m.variance = variance;
@@ -372,6 +384,10 @@ group_moments(const char *fn, int kind, mgdk_bat *b1, mgdk_bat *b2, mgdk_bat *g,
 	m.avg = nullptr;
 	m.flags = fl.as<uint32_t>();
 	const void *p2 = v2 ? v2->theap : nullptr;
+	// k_moments leaves the groups of at least fp_parallel_min() candidate
+	// rows to the parallel form and says so in the flags
+	if (a.ci.n >= fp_parallel_min())
+		m.par_min = fp_parallel_min();
 	if (kind == ST_VAR)
 		launch_moments<ST_VAR>(v1->ttype, v1->theap, nullptr, m);
 	else if (kind == ST_COV)
@@ -382,6 +398,21 @@ group_moments(const char *fn, int kind, mgdk_bat *b1, mgdk_bat *b2, mgdk_bat *g,
 	if (!hip_ok(hipMemcpyAsync(h, fl.p, 4, hipMemcpyDeviceToHost, stream()), "memcpy") || !sync()) {
 		mgdk_BBPunfix(bn);
 		return nullptr;
+	}
+	if (h[0] & 4) {
+		// one grid over the flat tile table of all large groups, one block
+		// per group to combine its tiles and take the result step
+		ProfScope pseg("groupstats_fp_seg");
+		FpSegs ls;
+		void *part = nullptr;
+		bool done = fp_large_segments(gr.start_p, ng, a.ci.n, m.par_min, ls) == 0 && ls.nseg > 0 &&
+			    seg_moments(kind, v1->ttype, v1->theap, p2, m, ls, &part) == 0 &&
+			    hip_ok(hipMemcpyAsync(h, fl.p, 4, hipMemcpyDeviceToHost, stream()), "memcpy") && sync();
+		dfree(part);
+		if (!done) {
+			mgdk_BBPunfix(bn);
+			return nullptr;
+		}
 	}
 	const uint32_t f = h[0];
 	if (f & 1) {
@@ -541,6 +572,163 @@ launch_mom_par(int tt, const void *v1, const void *v2, BUN n, MomState *part, un
 	}
 }
 
+// ---- the parallel form of the large groups of a grouped call ----------------
+// Block t folds tile t of the flat tile table (fp_large_segments) -- lane l
+// the positions l, l + 256, ... of it, through perm -- with k_mom_par's step;
+// one block per large group then combines that group's tiles in tile order
+// and takes the grouped result step of k_moments.  MomState::n also carries
+// what ends a group early in the replay: MOM_NIL a nil row without skip_nils
+// (the group's result is nil), MOM_INF an infinite accumulator in a lane, a
+// tile or a combined state (the call fails with the overflow error).
+constexpr double MOM_NIL = -1, MOM_INF = -2;
+
+template <int KIND>
+__device__ __forceinline__ MomState
+mom_comb_seg(const MomState &a, const MomState &b)
+{
+	if (a.n == MOM_NIL || b.n == MOM_NIL)
+		return a.n == MOM_NIL ? a : b;
+	if (a.n == MOM_INF || b.n == MOM_INF)
+		return a.n == MOM_INF ? a : b;
+	MomState r = mom_comb<KIND>(a, b);
+	if (mom_inf<KIND>(r))
+		r.n = MOM_INF;
+	return r;
+}
+
+template <typename T, int KIND>
+__global__ __launch_bounds__(256) void
+k_mom_seg(const T *v1, const T *v2, MomArgs a, const FpTile *tiles, MomState *part)
+{
+	__shared__ MomState lds[256];
+	const FpTile t = tiles[blockIdx.x];
+	MomState s{0, 0, 0, 0, 0, 0};
+	unsigned long long cnt = 0;
+	bool nil = false;
+	for (BUN j = t.first + threadIdx.x; j < t.last; j += 256) {
+		const BUN r = a.perm ? a.perm[j] : j;
+		if (!a.start) {
+			// one group: every candidate row, its id range-checked
+			const oid g = a.gids ? a.gids[r] : a.gseq + r;
+			if (g < a.gmin || g - a.gmin >= a.ngrp)
+				continue;
+		}
+		const T x = v1[a.off + r];
+		T y{};
+		if (KIND != ST_VAR)
+			y = v2[a.off + r];
+		if (is_nil(x) || (KIND != ST_VAR && is_nil(y))) {
+			nil |= !a.skip_nils;
+			continue;
+		}
+		const double nn = (double) ++cnt;
+		const double xd = to_dbl(x);
+		const double delta1 = xd - s.mean1;
+		s.mean1 += delta1 / nn;
+		if (KIND == ST_VAR) {
+			s.m2 += delta1 * (xd - s.mean1);
+		} else {
+			const double yd = to_dbl(y);
+			const double delta2 = yd - s.mean2;
+			s.mean2 += delta2 / nn;
+			if (KIND == ST_COV) {
+				s.m2 += delta1 * (yd - s.mean2);
+			} else {
+				const double aux = yd - s.mean2;
+				s.m2 += delta1 * aux;
+				s.down1 += delta1 * (xd - s.mean1);
+				s.down2 += delta2 * aux;
+			}
+		}
+	}
+	s.n = nil ? MOM_NIL : mom_inf<KIND>(s) ? MOM_INF : (double) cnt;
+	s = block_tree(s, [](const MomState &x, const MomState &y) { return mom_comb_seg<KIND>(x, y); }, lds);
+	if (threadIdx.x == 0)
+		part[blockIdx.x] = s;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void
+k_mom_seg_fin(const MomState *part, const FpSeg *segs, bool issample, bool variance, double *res, uint32_t *flags)
+{
+	__shared__ MomState lds[256];
+	const FpSeg sg = segs[blockIdx.x];
+	const unsigned nb = sg.nb, per = (nb + 255) / 256, p0 = min(nb, threadIdx.x * per), p1 = min(nb, p0 + per);
+	MomState s{0, 0, 0, 0, 0, 0};
+	for (unsigned p = p0; p < p1; p++)
+		s = mom_comb_seg<KIND>(s, part[sg.tile0 + p]);
+	s = block_tree(s, [](const MomState &x, const MomState &y) { return mom_comb_seg<KIND>(x, y); }, lds);
+	if (threadIdx.x != 0)
+		return;
+	// the grouped result step of k_moments
+	const double nil = __builtin_nan("");
+	const bool gnil = s.n == MOM_NIL;
+	const unsigned long long cnt = s.n > 0 ? (unsigned long long) s.n : 0;
+	double r;
+	bool isnil = false, ovf = false;
+	if (s.n == MOM_INF) {
+		r = nil;
+		ovf = true;
+	} else if (KIND == ST_COR) {
+		if (cnt <= 1 || gnil || s.down1 == 0 || s.down2 == 0) {
+			r = nil;
+			isnil = true;
+		} else {
+			r = (s.m2 / s.n) / (sqrt(s.down1 / s.n) * sqrt(s.down2 / s.n));
+		}
+	} else if (cnt == 0 || gnil) {
+		r = nil;
+		isnil = true;
+	} else if (cnt == 1) {
+		r = issample ? nil : 0.0;
+		isnil = issample;
+	} else {
+		r = s.m2 / (double) (cnt - (issample ? 1 : 0));
+		if (KIND == ST_VAR && !variance)
+			r = sqrt(r);
+	}
+	res[sg.id] = r;
+	const uint32_t f = (ovf ? 1u : 0u) | (isnil ? 2u : 0u);
+	if (f)
+		atomicOr(flags, f);
+}
+
+template <int KIND>
+void
+launch_mom_seg(int tt, const void *v1, const void *v2, const MomArgs &m, const FpSegs &ls, MomState *part)
+{
+	const dim3 grid((unsigned) ls.ntile), blk(256);
+	hipStream_t st = stream();
+	switch (tt) {
+	case MGDK_bte: hipLaunchKernelGGL((k_mom_seg<int8_t, KIND>), grid, blk, 0, st, (const int8_t *) v1, (const int8_t *) v2, m, ls.tiles, part); break;
+	case MGDK_sht: hipLaunchKernelGGL((k_mom_seg<int16_t, KIND>), grid, blk, 0, st, (const int16_t *) v1, (const int16_t *) v2, m, ls.tiles, part); break;
+	case MGDK_int: hipLaunchKernelGGL((k_mom_seg<int32_t, KIND>), grid, blk, 0, st, (const int32_t *) v1, (const int32_t *) v2, m, ls.tiles, part); break;
+	case MGDK_lng: hipLaunchKernelGGL((k_mom_seg<int64_t, KIND>), grid, blk, 0, st, (const int64_t *) v1, (const int64_t *) v2, m, ls.tiles, part); break;
+	case MGDK_hge: hipLaunchKernelGGL((k_mom_seg<hge, KIND>), grid, blk, 0, st, (const hge *) v1, (const hge *) v2, m, ls.tiles, part); break;
+	case MGDK_flt: hipLaunchKernelGGL((k_mom_seg<float, KIND>), grid, blk, 0, st, (const float *) v1, (const float *) v2, m, ls.tiles, part); break;
+	default: hipLaunchKernelGGL((k_mom_seg<double, KIND>), grid, blk, 0, st, (const double *) v1, (const double *) v2, m, ls.tiles, part); break;
+	}
+	hipLaunchKernelGGL((k_mom_seg_fin<KIND>), dim3((unsigned) ls.nseg), blk, 0, st, (const MomState *) part, ls.segs,
+			   m.issample, m.variance, m.res, m.flags);
+}
+
+// queues the kernels; *part (the tiles' states) is the caller's to free once
+// the stream is idle
+int
+seg_moments(int kind, int tt, const void *v1, const void *v2, const MomArgs &m, const FpSegs &ls, void **part)
+{
+	*part = dalloc((size_t) ls.ntile * sizeof(MomState));
+	if (*part == nullptr)
+		return -1;
+	if (kind == ST_VAR)
+		launch_mom_seg<ST_VAR>(tt, v1, v2, m, ls, (MomState *) *part);
+	else if (kind == ST_COV)
+		launch_mom_seg<ST_COV>(tt, v1, v2, m, ls, (MomState *) *part);
+	else
+		launch_mom_seg<ST_COR>(tt, v1, v2, m, ls, (MomState *) *part);
+	return 0;
+}
+
 // calcvariance / calccovariance / BATcalccorrelation over the whole column
 double
 calc_moments(int kind, double *avgp, mgdk_bat *b1, mgdk_bat *b2, bool issample, bool variance)
@@ -569,6 +757,7 @@ calc_moments(int kind, double *avgp, mgdk_bat *b1, mgdk_bat *b2, bool issample, 
 	m.ngrp = 1;
 	m.n = b1->count;
 	m.all = true;
+	m.par_min = MGDK_BUN_NONE;
 	m.skip_nils = true;
 	m.issample = issample;
 	m.variance = variance;

@@ -322,6 +322,67 @@ struct GroupRows {
 };
 int group_rows(const AggrInit &a, GroupRows &gr);
 
+// ---- the large segments of an order-dependent float fold -------------------
+// A group / partition of at least fp_parallel_min() candidate rows (nils
+// included) takes the parallel form beside the replayed smaller ones
+// (DESIGN.md 11.5).  It is cut into tiles by its own length alone -- the rule
+// of the one-group form -- so its result depends on its own values in
+// candidate order and on the threshold, not on what else the call holds.
+__host__ __device__ inline bool
+fp_large(BUN len, BUN thr)
+{
+	return len > 0 && len >= thr;
+}
+// tiles of a segment of len > 0 positions (and the positions per tile):
+// ~16 per lane of a 256-thread block, at most 2048 tiles; or tiles of
+// `fixed` positions each (the running sum's scan tiles)
+__host__ __device__ inline unsigned
+fp_tiling(BUN len, BUN *tile, BUN fixed = 0)
+{
+	if (fixed) {
+		*tile = fixed;
+		return (unsigned) ((len + fixed - 1) / fixed);
+	}
+	const unsigned nb = (unsigned) (len + 4095 < (BUN) 2048 * 4096 ? (len + 4095) / 4096 : 2048);
+	*tile = (len + nb - 1) / nb;
+	return (unsigned) ((len + *tile - 1) / *tile);
+}
+struct FpSeg {
+	uint64_t id;            // group / partition index
+	uint64_t first, len;    // its positions [first, first + len)
+	uint64_t tile0;         // its first slot in the tile table
+	uint32_t nb;            // its tiles
+	uint32_t pad;
+};
+struct FpTile {
+	uint32_t seg;           // index into the list of large segments
+	uint32_t tix;           // tile index within the segment
+	uint64_t first, last;   // positions [first, last)
+};
+// the large segments among nseg segments given by nseg + 1 offsets (start
+// NULL: one segment [0, n)), in segment order, and the flat table of their
+// tiles: three small kernels and two scans whatever the number of large
+// segments; nothing is launched when n < thr (no segment can be large).
+// The callers come here only after their replay kernel, which skips the
+// large segments by the same test, has reported one.
+struct FpSegs {
+	FpSeg *segs = nullptr;
+	FpTile *tiles = nullptr;
+	uint64_t *toff = nullptr, *loff = nullptr;   // the scans' results, read by the queued kernels
+	BUN nseg = 0, ntile = 0;
+	FpSegs() = default;
+	~FpSegs()
+	{
+		dfree(segs);
+		dfree(tiles);
+		dfree(toff);
+		dfree(loff);
+	}
+	FpSegs(const FpSegs &) = delete;
+	FpSegs &operator=(const FpSegs &) = delete;
+};
+int fp_large_segments(const uint64_t *start, BUN nseg, BUN n, BUN thr, FpSegs &ls, BUN fixed_tile = 0);
+
 }  // namespace mgdk
 
 

@@ -4,7 +4,15 @@ form (the default from 2^20 rows), with the oracle's sequential C loop on a
 10M-row sample beside them.
 
     python tools/fp_cliff.py [rows]      -> one JSON object on stdout
+
+With --groups K and / or --partitions K (default 4) the same over K equal
+segments instead: the grouped dbl average and stdev over K interleaved
+groups, the running dbl SUM over K contiguous partitions, replay against
+parallel.  --small-groups G times the grouped average and stdev over G
+small groups (none reaches the threshold) at the default knob; --reps N
+sets the timed repetitions.  A trailing "par" skips the replay legs.
 """
+import argparse
 import json
 import os
 import sys
@@ -28,9 +36,61 @@ def timed(fn, reps):
     return out, (time.perf_counter() - t) / reps * 1e3
 
 
+def segments(n, ngroups, nparts, nsmall, par_only, reps):
+    """replay against parallel over several equal groups / partitions"""
+    gdk.init(0)
+    r = np.random.default_rng(5)
+    x = r.standard_normal(n) * 100.0 + 50.0
+    B = gdk.BAT.from_numpy(gdk.TYPE_dbl, x, sorted_=False, revsorted=False, key=False)
+    ops = {}
+    if ngroups or nsmall:
+        k = ngroups or nsmall
+        g = gdk.BAT.from_numpy(gdk.TYPE_oid, np.arange(n, dtype=np.uint64) % np.uint64(k), sorted_=False,
+                               revsorted=False, key=False)
+        e = gdk.BAT.dense(0, k)
+        tag = "%d_groups" % k
+        ops["groupavg_" + tag] = lambda: gdk.BATgroupavg(B, g, e, True)[0]
+        ops["groupstdev_" + tag] = lambda: gdk.BATgroupstdev_population(B, g, e, True)
+    if nparts:
+        p = np.zeros(n, np.int8)
+        p[::(n + nparts - 1) // nparts] = 1
+        o = p.copy()
+        o[::16] = 1                   # peer groups of 16 rows
+        P, O = gdk.BAT.from_numpy(gdk.TYPE_bit, p), gdk.BAT.from_numpy(gdk.TYPE_bit, o)
+        ops["running_sum_%d_partitions" % nparts] = lambda: gdk.GDKanalyticalsum(B, P, O, None, None, gdk.TYPE_dbl, 3)
+    res = {"rows": n}
+    for name, dev in ops.items():
+        par, ms_par = timed(dev, reps)
+        d = {"parallel_ms" if not nsmall else "ms": round(ms_par, 3)}
+        if not par_only and not nsmall:
+            prev = gdk.set_fp_parallel_min(None)
+            try:
+                seq, ms_seq = timed(dev, 1)
+            finally:
+                gdk.set_fp_parallel_min(prev)
+            a, b = seq.to_numpy(), par.to_numpy()
+            d["replay_ms"] = round(ms_seq, 3)
+            d["max_abs_diff"] = float(np.nanmax(np.abs(a - b)))
+            d["max_abs_value"] = float(np.nanmax(np.abs(a)))
+        res[name] = d
+        print(json.dumps({name: d}), file=sys.stderr, flush=True)
+    print(json.dumps(res))
+
+
 def main():
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 100_000_000
-    par_only = len(sys.argv) > 2 and sys.argv[2] == "par"     # profiling runs: no replay, no oracle
+    ap = argparse.ArgumentParser()
+    ap.add_argument("rows", nargs="?", type=int, default=100_000_000)
+    ap.add_argument("par", nargs="?", choices=["par"])
+    ap.add_argument("--groups", nargs="?", type=int, const=4, default=0)
+    ap.add_argument("--partitions", nargs="?", type=int, const=4, default=0)
+    ap.add_argument("--small-groups", type=int, default=0)
+    ap.add_argument("--reps", type=int, default=5)
+    args = ap.parse_args()
+    n = args.rows
+    par_only = args.par == "par"     # profiling runs: no replay, no oracle
+    if args.groups or args.partitions or args.small_groups:
+        segments(n, 0 if args.small_groups else args.groups, args.partitions, args.small_groups, par_only, args.reps)
+        return
     ns = min(n, 10_000_000)
     gdk.init(0)
     r = np.random.default_rng(5)
