@@ -77,7 +77,13 @@ int mgdk_init(int device);                       /* select HIP device */
  * blocked folds combined pairwise (Chan et al. for the moments) -- whose
  * results differ from the sequential ones by rounding only, within the
  * bounds DESIGN.md states (a few n ulp); the smaller groups of the same call
- * stay bit-exact.  Process-wide; returns the previous value. */
+ * stay bit-exact.  The window functions follow the same rule per partition
+ * (a single one counts, p == NULL included): mgdk_GDKanalyticalsum of
+ * flt / dbl (frames 3, 4), mgdk_GDKanalyticalavg of flt / dbl (frames 3, 5)
+ * and the seven mgdk_GDKanalytical_* statistics of every type (frames 3, 4,
+ * 5), with the bounds applied to each row's fold prefix.  Products
+ * (mgdk_GDKanalyticalprod, float BATgroupprod) are always replayed.
+ * Process-wide; returns the previous value. */
 mgdk_BUN mgdk_set_fp_parallel_min(mgdk_BUN rows);
 const char *mgdk_GDKerrbuf(void);                /* gdk.h:1947 GDKerrbuf */
 void mgdk_GDKclrerr(void);

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "mgdk_internal.h"
+#include "fpfold.h"
 
 using namespace mgdk;
 
@@ -1798,30 +1799,7 @@ k_favg_replay(const T *vals, oid off, const uint32_t *perm, const uint64_t *star
 // the lanes and blocks are merged in order, (a, c) + (b, d) -> a + (b - a) *
 // (d / (c + d)): the weighted mean of the partial means.  Only the rounding
 // differs from the sequential fold (DESIGN.md states the bound).
-struct FAvg {
-	double a;
-	double c;
-	int nil;
-};
-
-__device__ __forceinline__ FAvg
-favg_comb(const FAvg &x, const FAvg &y)
-{
-	FAvg r;
-	r.nil = x.nil | y.nil;
-	if (x.c == 0) {
-		r.a = y.a;
-		r.c = y.c;
-	} else if (y.c == 0) {
-		r.a = x.a;
-		r.c = x.c;
-	} else {
-		r.c = x.c + y.c;
-		r.a = x.a + (y.a - x.a) * (y.c / r.c);
-	}
-	return r;
-}
-
+// (FAvg, favg_comb: fpfold.h)
 template <typename T>
 __global__ __launch_bounds__(256) void
 k_favg_par(const T *vals, oid off, const oid *gids, oid gseq, oid gmin, BUN n, BUN tile, bool skip_nils, FAvg *part)

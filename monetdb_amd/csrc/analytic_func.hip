@@ -31,6 +31,8 @@
 
 #include "mgdk_internal.h"
 #include "segments.h"
+#include "fpfold.h"
+#include "runscan.h"
 
 using namespace mgdk;
 
@@ -787,8 +789,9 @@ out:
 // dependent:
 //   * flt / dbl over frames 3 and 5: AVERAGE_ITER_FLOAT in the input type,
 //     row by row through the partition -- one lane per partition
-//     (k_avg_replay); frame 4 of flt / dbl never assigns its result (:224-246),
-//     so every row is nil;
+//     (k_avg_replay), the partitions of at least fp_parallel_min() rows as a
+//     blocked scan instead (FAvgScan); frame 4 of flt / dbl never assigns its
+//     result (:224-246), so every row is nil;
 //   * general frames: the reference's fanout-16 segment tree per partition
 //     (gdk_analytic.h:63-130) whose inner nodes fold their non-empty
 //     children's averages with AVERAGE_ITER / AVERAGE_ITER_FLOAT (a node
@@ -1021,11 +1024,15 @@ k_avg_tree_query(const T *b, Starts part, const uint32_t *pidx, AvgTree t, const
 // / _ALL_ROWS, gdk_analytic_statistics.c:202-267)
 template <typename T>
 __global__ __launch_bounds__(64) void
-k_avg_replay(const T *b, Starts part, const int8_t *o, bool peers, double *out, uint32_t *flags)
+k_avg_replay(const T *b, Starts part, const int8_t *o, bool peers, double *out, uint32_t *flags, BUN par_min)
 {
 	const BUN k = (BUN) blockIdx.x * blockDim.x + threadIdx.x;
 	uint32_t hasnil = 0;
-	if (k < part.m) {
+	// a large partition is left to the parallel form (FAvgScan): flag bit 3
+	// tells the host that there is one
+	if (k < part.m && fp_large(part.end_of(k) - part.at(k), par_min)) {
+		publish_or(flags, 8);
+	} else if (k < part.m) {
 		const BUN ps = part.at(k), pe = part.end_of(k);
 		AvgNode<T> c;
 		c.zero();
@@ -1048,6 +1055,47 @@ k_avg_replay(const T *b, Starts part, const int8_t *o, bool peers, double *out, 
 	if (hasnil)
 		publish_or(flags, 1);
 }
+
+// The parallel form of a large partition (fp_parallel_min): the running mean
+// as the blocked scan of runscan.h over (mean, count) states merged by
+// favg_comb, accumulated in double; the result is rounded to the input type
+// first, as the reference's average is a value of that type.  Only the
+// rounding differs from the replay (DESIGN.md states the bound).
+template <typename T>
+struct FAvgScan {
+	using State = FAvg;
+	using Out = double;
+	using Raw = T;
+	static constexpr unsigned TPT = 8;
+	struct Stage {
+		T v[RS_SLOTS];
+	};
+	const T *b;
+	__device__ __forceinline__ void stage(Stage &sg, unsigned slot, BUN row) const { sg.v[slot] = b[row]; }
+	__device__ __forceinline__ void stage_none(Stage &sg, unsigned slot) const { sg.v[slot] = (T) 0; }
+	__device__ __forceinline__ Raw raw(const Stage &sg, unsigned slot) const { return sg.v[slot]; }
+	__device__ __forceinline__ State leaf(const Raw &v, bool valid) const
+	{
+		const bool has = valid && v == v;
+		return State{has ? (double) v : 0.0, has ? 1.0 : 0.0, 0};
+	}
+	static __device__ __forceinline__ State zero() { return State{0, 0, 0}; }
+	static __device__ __forceinline__ State comb(const State &a, const State &b, uint32_t &) { return favg_comb(a, b); }
+	static __device__ __forceinline__ State shfl_up(const State &v, int d)
+	{
+		return State{__shfl_up(v.a, d), __shfl_up(v.c, d), 0};
+	}
+	__device__ __forceinline__ Out result(const State &s, bool end, uint32_t &fl) const
+	{
+		if (!end)
+			return 0;
+		if (s.c == 0) {
+			fl |= 1;
+			return __builtin_nan("");
+		}
+		return (double) (T) s.a;
+	}
+};
 
 template <typename T>
 __global__ __launch_bounds__(256) void
@@ -1096,6 +1144,8 @@ run_avg(mgdk_bat *r, mgdk_bat *p, mgdk_bat *o, mgdk_bat *b, mgdk_bat *s, mgdk_ba
 		return -1;
 	mgdk_bat *Sp = nullptr;
 	int rc = -1;
+	Starts part{};
+	BUN par_min = MGDK_BUN_NONE;
 	if (IOUT && frame_type == 6) {
 		hipLaunchKernelGGL((k_avg_copy<T>), dim3(grid_for(n, 1024, 8192)), dim3(256), 0, st, bv, n, (T *) out,
 				   fl.as<uint32_t>());
@@ -1103,15 +1153,18 @@ run_avg(mgdk_bat *r, mgdk_bat *p, mgdk_bat *o, mgdk_bat *b, mgdk_bat *s, mgdk_ba
 		hipLaunchKernelGGL((k_avg_row<T>), dim3(grid_for(n, 1024, 8192)), dim3(256), 0, st, bv, n,
 				   frame_type == 4, (double *) out, fl.as<uint32_t>());
 	} else {
-		Starts part;
 		if (make_starts(p ? (const int8_t *) p->theap : nullptr, n, part, &Sp) < 0)
 			goto out;
 		if (!frames) {
-			// flt / dbl, frames 3 and 5 (integers take run_frames)
-			if constexpr (isf)
+			// flt / dbl, frames 3 and 5 (integers take run_frames); the
+			// partitions of at least fp_parallel_min() rows are left to
+			// rs_run_large below
+			if constexpr (isf) {
+				par_min = n >= fp_parallel_min() ? fp_parallel_min() : (BUN) MGDK_BUN_NONE;
 				hipLaunchKernelGGL((k_avg_replay<T>), dim3((unsigned) ((part.m + 63) / 64)), dim3(64), 0, st, bv,
 						   part, frame_type == 3 ? (const int8_t *) o->theap : nullptr, frame_type == 3,
-						   (double *) out, fl.as<uint32_t>());
+						   (double *) out, fl.as<uint32_t>(), par_min);
+			}
 		} else {
 			if (n >= 0xffffffffull) {
 				seterr("42000!GDKanalyticalavg: more than 2^32-1 rows on the device path\n");
@@ -1159,9 +1212,19 @@ run_avg(mgdk_bat *r, mgdk_bat *p, mgdk_bat *o, mgdk_bat *b, mgdk_bat *s, mgdk_ba
 		uint32_t *h = (uint32_t *) pinned(16);
 		if (!hip_ok(hipMemcpyAsync(h, fl.p, 4, hipMemcpyDeviceToHost, st), "memcpy") || !sync())
 			goto out;
+		if constexpr (isf && !IOUT) {
+			if (h[0] & 8) {
+				// the replay of frames 3 / 5 left large partitions out
+				ProfScope pseg("analyticalavg_fp_seg");
+				if (rs_run_large(FAvgScan<T>{bv}, part, frame_type == 3 ? (const int8_t *) o->theap : nullptr, n,
+						 par_min, true, frame_type == 5, (double *) out, fl.as<uint32_t>()) < 0 ||
+				    !hip_ok(hipMemcpyAsync(h, fl.p, 4, hipMemcpyDeviceToHost, st), "memcpy") || !sync())
+					goto out;
+			}
+		}
 		r->count = n;
-		r->tnil = h[0] != 0;
-		r->tnonil = h[0] == 0;
+		r->tnil = (h[0] & 1) != 0;
+		r->tnonil = (h[0] & 1) == 0;
 		r->tsorted = r->trevsorted = r->tkey = n <= 1;
 		rc = 0;
 	}
@@ -1401,483 +1464,73 @@ k_fsum_tree_query(const T1 *b, Starts part, const uint32_t *pidx, AvgTree t, con
 		publish_or(flags, fl);
 }
 
-// ---- the parallel form of frames 3 / 4 over one partition ----------------
-// (fp_parallel_min): the running sum as a blocked scan.  Positions q are
-// rows in fold order (frame 3: q = row; frame 4: q = n - 1 - row); a
-// position ends its peer run where the replay writes (frame 3: o[row + 1]
-// or the last row; frame 4: o[row] or row 0).  Pass 1 folds each 4096-
-// position tile (16 per lane, the lanes combined in order); pass 2 scans
-// the tile totals; pass 3 writes every position's running sum; pass 4 gives
-// every position the sum at the end of its run (end positions are never
-// rewritten, so it reads them in place).  FSum::fold keeps the replay's
-// overflow test and nil rule; only the rounding differs (DESIGN.md states
-// the bound).
-constexpr unsigned RS_PER = 16, RS_TILE = 256 * RS_PER;
-
-__device__ __forceinline__ BUN
-rs_row(BUN q, BUN n, bool fwd)
-{
-	return fwd ? q : n - 1 - q;
-}
-
-__device__ __forceinline__ bool
-rs_end(const int8_t *o, BUN q, BUN n, bool fwd)
-{
-	if (fwd)
-		return q + 1 == n || o[q + 1];
-	const BUN j = n - 1 - q;
-	return j == 0 || o[j];
-}
-
-template <typename T2>
-__device__ __forceinline__ FSum<T2>
-rs_comb(FSum<T2> a, const FSum<T2> &b, uint32_t &fl)
-{
-	if (!a.fold(b))
-		fl |= 2;
-	return a;
-}
-
-// a lane's RS_PER positions q0 .. q0 + RS_PER - 1 of its tile: values (as
-// FSum leaves) and run-end flags.  The tile's values and end bytes are
-// loaded row-wise (consecutive lanes, consecutive addresses) into LDS and
-// each lane then reads its RS_PER consecutive positions (one pad slot per
-// RS_PER keeps those reads off a single bank)
-template <typename T1>
-struct RsStage {
-	T1 v[RS_TILE + RS_TILE / RS_PER];
-	int8_t f[RS_TILE];
-};
-
+// ---- the parallel form of frames 3 / 4 ----------------------------------
+// (fp_parallel_min): the running sum as the blocked scan of runscan.h.
+// FSum::fold keeps the replay's overflow test and nil rule; only the
+// rounding differs (DESIGN.md states the bound).
 template <typename T1, typename T2>
-__device__ __forceinline__ void
-rs_load(const T1 *b, const int8_t *o, BUN n, bool fwd, BUN tb, RsStage<T1> &sg, FSum<T2> (&x)[RS_PER],
-	bool (&e)[RS_PER])
-{
-	const BUN t0 = tb * RS_TILE;
-#pragma unroll
-	for (unsigned k = 0; k < RS_PER; k++) {
-		const unsigned i = k * 256 + threadIdx.x;
-		const BUN q = t0 + i;
-		T1 v = (T1) 0;
-		int8_t f = 1;
-		if (q < n) {
-			v = b[rs_row(q, n, fwd)];
-			// the end flag's byte: o[q + 1] (frame 3) or o[n - 1 - q] (frame
-			// 4); the last position always ends its run
-			if (q + 1 < n)
-				f = o[fwd ? q + 1 : n - 1 - q];
-		}
-		sg.v[i + i / RS_PER] = v;
-		sg.f[i] = f;
+struct FSumScan {
+	using State = FSum<T2>;
+	using Out = T2;
+	using Raw = T1;
+	static constexpr unsigned TPT = 32;
+	struct Stage {
+		T1 v[RS_SLOTS];
+	};
+	const T1 *b;
+	__device__ __forceinline__ void stage(Stage &sg, unsigned slot, BUN row) const { sg.v[slot] = b[row]; }
+	__device__ __forceinline__ void stage_none(Stage &sg, unsigned slot) const { sg.v[slot] = (T1) 0; }
+	__device__ __forceinline__ Raw raw(const Stage &sg, unsigned slot) const { return sg.v[slot]; }
+	__device__ __forceinline__ State leaf(const Raw &v, bool valid) const
+	{
+		State x;
+		x.nil = !valid || v != v;
+		x.v = x.nil ? (T2) 0 : (T2) v;
+		return x;
 	}
-	__syncthreads();
-	const unsigned l0 = threadIdx.x * RS_PER;
-#pragma unroll
-	for (unsigned k = 0; k < RS_PER; k++) {
-		const unsigned i = l0 + k;
-		const BUN q = t0 + i;
-		const T1 v = sg.v[i + i / RS_PER];
-		x[k].nil = q >= n || v != v;
-		x[k].v = x[k].nil ? (T2) 0 : (T2) v;
-		e[k] = q < n && sg.f[i] != 0;
+	static __device__ __forceinline__ State zero()
+	{
+		State z;
+		z.zero();
+		return z;
 	}
-}
-
-template <typename T2>
-__device__ __forceinline__ FSum<T2>
-rs_shfl_up(const FSum<T2> &v, int d)
-{
-	FSum<T2> y;
-	y.v = __shfl_up(v.v, d);
-	y.nil = __shfl_up(v.nil, d);
-	return y;
-}
-
-// ordered exclusive scan over the block's values (blockDim.x a multiple of
-// 64, at most 1024): a wave scan by shuffles, then the waves' totals through
-// LDS (one barrier); the same association every launch.  *total = the fold
-// of all of them
-template <typename T2>
-__device__ __forceinline__ FSum<T2>
-rs_block_excl(FSum<T2> v, FSum<T2> *wt, uint32_t &fl, FSum<T2> *total)
-{
-	const unsigned lane = __lane_id(), w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-	FSum<T2> inc = v;
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) {
-		const FSum<T2> y = rs_shfl_up(inc, d);
-		if ((int) lane >= d)
-			inc = rs_comb(y, inc, fl);
+	static __device__ __forceinline__ State comb(State a, const State &b, uint32_t &fl)
+	{
+		if (!a.fold(b))
+			fl |= 2;
+		return a;
 	}
-	FSum<T2> ex = rs_shfl_up(inc, 1);
-	if (lane == 0)
-		ex.zero();
-	if (lane == 63)
-		wt[w] = inc;
-	__syncthreads();
-	FSum<T2> wp, all;
-	wp.zero();
-	all.zero();
-	for (unsigned q = 0; q < nw; q++) {
-		if (q < w)
-			wp = rs_comb(wp, wt[q], fl);
-		all = rs_comb(all, wt[q], fl);
+	static __device__ __forceinline__ State shfl_up(const State &v, int d)
+	{
+		State y;
+		y.v = __shfl_up(v.v, d);
+		y.nil = __shfl_up(v.nil, d);
+		return y;
 	}
-	*total = all;
-	__syncthreads();            // wt may be reused by the caller
-	return rs_comb(wp, ex, fl);
-}
-
-// (tb: the tile's index within its partition, slot: its place in tot / fend;
-// the same number with one partition)
-template <typename T1, typename T2>
-__device__ __forceinline__ void
-rs_tile_body(const T1 *b, const int8_t *o, BUN n, bool fwd, BUN tb, BUN slot, FSum<T2> *tot, BUN *fend,
-	     uint32_t *flags)
-{
-	__shared__ FSum<T2> lds[256];
-	__shared__ BUN sm[256];
-	__shared__ RsStage<T1> sg;
-	const BUN q0 = tb * RS_TILE + threadIdx.x * RS_PER;
-	FSum<T2> x[RS_PER];
-	bool e[RS_PER];
-	rs_load<T1, T2>(b, o, n, fwd, tb, sg, x, e);
-	FSum<T2> acc;
-	acc.zero();
-	BUN fe = ~(BUN) 0;
-	uint32_t fl = 0;
-#pragma unroll
-	for (int k = (int) RS_PER - 1; k >= 0; k--)
-		if (e[k])
-			fe = q0 + k;
-#pragma unroll
-	for (unsigned k = 0; k < RS_PER; k++)
-		acc = rs_comb(acc, x[k], fl);
-	FSum<T2> total;
-	(void) rs_block_excl(acc, lds, fl, &total);
-#pragma unroll
-	for (int d = 32; d > 0; d >>= 1)
-		fe = min(fe, (BUN) __shfl_xor(fe, d));
-	if (__lane_id() == 0)
-		sm[threadIdx.x >> 6] = fe;
-	__syncthreads();
-	fe = min(min(sm[0], sm[1]), min(sm[2], sm[3]));
-	if (threadIdx.x == 0) {
-		tot[slot] = total;
-		fend[slot] = fe;
-	}
-	if (fl)
-		atomicOr(flags, fl);
-}
-
-template <typename T1, typename T2>
-__global__ __launch_bounds__(256) void
-k_rs_tile(const T1 *b, const int8_t *o, BUN n, bool fwd, FSum<T2> *tot, BUN *fend, uint32_t *flags)
-{
-	rs_tile_body<T1, T2>(b, o, n, fwd, blockIdx.x, blockIdx.x, tot, fend, flags);
-}
-
-// the same over the flat tile table of the large partitions: a tile's
-// positions are counted within its partition (frame 4 backwards within it),
-// whose first row (frame 4) or last row (frame 3) ends a run
-template <typename T1, typename T2>
-__global__ __launch_bounds__(256) void
-k_rs_tile_seg(const T1 *b, const int8_t *o, bool fwd, const FpSeg *segs, const FpTile *tiles, FSum<T2> *tot,
-	      BUN *fend, uint32_t *flags)
-{
-	const FpTile t = tiles[blockIdx.x];
-	const FpSeg sg = segs[t.seg];
-	rs_tile_body<T1, T2>(b + sg.first, o + sg.first, sg.len, fwd, t.tix, blockIdx.x, tot, fend, flags);
-}
-
-// pre[t] = the fold of the tiles before t (in order); nxt[t] = the first run
-// end at or after tile t + 1's first position.  One workgroup of 1024
-// threads: thread t folds a contiguous run of tiles (its loads issued
-// together), one block scan of the runs, then each thread writes its run's
-// prefixes; the suffix minima alike
-constexpr unsigned RS_TPT = 32;     // tiles per thread per round (all loaded at once)
-
-template <typename T2>
-__device__ __forceinline__ void
-rs_tiles_body(const FSum<T2> *tot, const BUN *fend, BUN nt, FSum<T2> *pre, BUN *nxt, uint32_t *flags)
-{
-	__shared__ FSum<T2> wt[16];
-	__shared__ BUN wm[16];
-	uint32_t fl = 0;
-	FSum<T2> carry;
-	carry.zero();
-	const BUN round = (BUN) 1024 * RS_TPT;
-	for (BUN r0 = 0; r0 < nt; r0 += round) {
-		const BUN b0 = r0 + (BUN) threadIdx.x * RS_TPT;
-		FSum<T2> v[RS_TPT];
-#pragma unroll
-		for (unsigned k = 0; k < RS_TPT; k++) {
-			if (b0 + k < nt)
-				v[k] = tot[b0 + k];
-			else
-				v[k].zero();
-		}
-		FSum<T2> acc;
-		acc.zero();
-#pragma unroll
-		for (unsigned k = 0; k < RS_TPT; k++)
-			acc = rs_comb(acc, v[k], fl);
-		FSum<T2> total;
-		FSum<T2> run = rs_comb(carry, rs_block_excl(acc, wt, fl, &total), fl);
-#pragma unroll
-		for (unsigned k = 0; k < RS_TPT; k++) {
-			if (b0 + k < nt)
-				pre[b0 + k] = run;
-			run = rs_comb(run, v[k], fl);
-		}
-		carry = rs_comb(carry, total, fl);
-	}
-	// suffix minima of the first ends, rounds from the back
-	BUN m = ~(BUN) 0;
-	const BUN nr = (nt + round - 1) / round;
-	const unsigned lane = __lane_id(), w = threadIdx.x >> 6;
-	for (BUN rr = nr; rr-- > 0;) {
-		const BUN b0 = rr * round + (BUN) threadIdx.x * RS_TPT;
-		BUN f[RS_TPT];
-		BUN own = ~(BUN) 0;
-#pragma unroll
-		for (unsigned k = 0; k < RS_TPT; k++) {
-			f[k] = b0 + k < nt ? fend[b0 + k] : ~(BUN) 0;
-			own = min(own, f[k]);
-		}
-		// minimum over the threads after this one: wave suffix minimum,
-		// then the later waves
-		BUN suf = own;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const BUN y = (BUN) __shfl_down(suf, d);
-			if ((int) lane + d < 64)
-				suf = min(suf, y);
-		}
-		if (lane == 0)
-			wm[w] = suf;
-		__syncthreads();
-		BUN later = m;
-		for (unsigned q = w + 1; q < 16; q++)
-			later = min(later, wm[q]);
-		const BUN nextin = (BUN) __shfl_down(suf, 1);
-		BUN after = lane + 1 < 64 ? min(nextin, later) : later;
-		const BUN rmin = min(min(min(wm[0], wm[1]), min(wm[2], wm[3])),
-				     min(min(min(wm[4], wm[5]), min(wm[6], wm[7])),
-					 min(min(min(wm[8], wm[9]), min(wm[10], wm[11])),
-					     min(min(wm[12], wm[13]), min(wm[14], wm[15])))));
-		__syncthreads();
-#pragma unroll
-		for (int k = (int) RS_TPT - 1; k >= 0; k--) {
-			if (b0 + k < nt)
-				nxt[b0 + k] = after;
-			after = min(after, f[k]);
-		}
-		m = min(m, rmin);
-	}
-	if (fl)
-		atomicOr(flags, fl);
-}
-
-template <typename T2>
-__global__ __launch_bounds__(1024) void
-k_rs_tiles(const FSum<T2> *tot, const BUN *fend, BUN nt, FSum<T2> *pre, BUN *nxt, uint32_t *flags)
-{
-	rs_tiles_body<T2>(tot, fend, nt, pre, nxt, flags);
-}
-
-// one workgroup per large partition: the scan restarts at its first tile
-template <typename T2>
-__global__ __launch_bounds__(1024) void
-k_rs_tiles_seg(const FpSeg *segs, const FSum<T2> *tot, const BUN *fend, FSum<T2> *pre, BUN *nxt, uint32_t *flags)
-{
-	const FpSeg sg = segs[blockIdx.x];
-	rs_tiles_body<T2>(tot + sg.tile0, fend + sg.tile0, sg.nb, pre + sg.tile0, nxt + sg.tile0, flags);
-}
-
-// pass 3: every position's value -- the running sum at the end of its peer
-// run when that end lies inside the tile (read back from LDS), else its own
-// running sum for now -- stored row-wise; pass 4 gives the positions of the
-// tile's open last run (its end in a later tile) that end's value, read
-// from the output in place (end positions are never rewritten)
-template <typename T1, typename T2>
-__device__ __forceinline__ void
-rs_write_body(const T1 *b, const int8_t *o, BUN n, bool fwd, BUN tb, BUN slot, const FSum<T2> *pre, const BUN *nxt,
-	      int pass, T2 *out, uint32_t *flags)
-{
-	__shared__ FSum<T2> ls[256];
-	__shared__ BUN lm[256];
-	__shared__ RsStage<T1> sg;
-	__shared__ T2 wo[RS_TILE + RS_TILE / RS_PER];
-	const BUN t0 = tb * RS_TILE;
-	const BUN q0 = t0 + threadIdx.x * RS_PER;
-	const BUN tend = t0 + RS_TILE < n ? t0 + RS_TILE : n;
-	uint32_t fl = 0;
-	FSum<T2> x[RS_PER];
-	bool e[RS_PER];
-	rs_load<T1, T2>(b, o, n, fwd, tb, sg, x, e);
-	// the first run end at or after each lane's chunk, inside the tile
-	BUN fe = ~(BUN) 0;
-#pragma unroll
-	for (int k = (int) RS_PER - 1; k >= 0; k--)
-		if (e[k])
-			fe = q0 + k;
-	lm[threadIdx.x] = fe;
-	__syncthreads();
-	for (unsigned d = 1; d < 256; d <<= 1) {
-		BUN y = lm[threadIdx.x];
-		if (threadIdx.x + d < 256)
-			y = min(y, lm[threadIdx.x + d]);
-		__syncthreads();
-		lm[threadIdx.x] = y;
-		__syncthreads();
-	}
-	const BUN after = threadIdx.x + 1 < 256 ? lm[threadIdx.x + 1] : ~(BUN) 0;
-	if (pass == 1) {
-		// the open last run: positions whose end is in a later tile
-		BUN endq = after != ~(BUN) 0 ? after : nxt[slot];
-		if (after != ~(BUN) 0)
-			return;      // this lane's positions all end inside the tile
-#pragma unroll
-		for (int k = (int) RS_PER - 1; k >= 0; k--) {
-			const BUN q = q0 + k;
-			if (q >= n)
-				continue;
-			if (e[k])
-				return;      // this position and the ones before it end inside the tile
-			out[rs_row(q, n, fwd)] = out[rs_row(endq, n, fwd)];
-		}
-		return;
-	}
-	FSum<T2> acc;
-	acc.zero();
-#pragma unroll
-	for (unsigned k = 0; k < RS_PER; k++)
-		acc = rs_comb(acc, x[k], fl);
-	FSum<T2> total;
-	const FSum<T2> ex = rs_block_excl(acc, ls, fl, &total);
-	FSum<T2> run = rs_comb(pre[slot], ex, fl);
-	const unsigned l0 = threadIdx.x * RS_PER;
-#pragma unroll
-	for (unsigned k = 0; k < RS_PER; k++) {
-		run = rs_comb(run, x[k], fl);
-		const unsigned i = l0 + k;
-		wo[i + i / RS_PER] = run.nil ? (T2) __builtin_nan("") : run.v;
-		if (run.nil && e[k])
+	__device__ __forceinline__ Out result(const State &run, bool end, uint32_t &fl) const
+	{
+		if (run.nil && end)
 			fl |= 1;
+		return run.nil ? (T2) __builtin_nan("") : run.v;
 	}
-	__syncthreads();
-	// positions take their run end's value when it is in the tile (end
-	// positions keep their own: nothing they read is rewritten)
-	BUN endq = after;
-#pragma unroll
-	for (int k = (int) RS_PER - 1; k >= 0; k--) {
-		const BUN q = q0 + k;
-		if (e[k]) {
-			endq = q;
-			continue;
-		}
-		if (endq != ~(BUN) 0 && q < n) {
-			const unsigned j = (unsigned) (endq - t0), i = l0 + k;
-			wo[i + i / RS_PER] = wo[j + j / RS_PER];
-		}
-	}
-	__syncthreads();
-#pragma unroll
-	for (unsigned k = 0; k < RS_PER; k++) {
-		const unsigned i = k * 256 + threadIdx.x;
-		if (t0 + i < tend)
-			out[rs_row(t0 + i, n, fwd)] = wo[i + i / RS_PER];
-	}
-	if (fl)
-		atomicOr(flags, fl);
-}
-
-template <typename T1, typename T2>
-__global__ __launch_bounds__(256) void
-k_rs_write(const T1 *b, const int8_t *o, BUN n, bool fwd, const FSum<T2> *pre, const BUN *nxt, int pass, T2 *out,
-	   uint32_t *flags)
-{
-	rs_write_body<T1, T2>(b, o, n, fwd, blockIdx.x, blockIdx.x, pre, nxt, pass, out, flags);
-}
-
-template <typename T1, typename T2>
-__global__ __launch_bounds__(256) void
-k_rs_write_seg(const T1 *b, const int8_t *o, bool fwd, const FpSeg *segs, const FpTile *tiles, const FSum<T2> *pre,
-	       const BUN *nxt, int pass, T2 *out, uint32_t *flags)
-{
-	const FpTile t = tiles[blockIdx.x];
-	const FpSeg sg = segs[t.seg];
-	rs_write_body<T1, T2>(b + sg.first, o + sg.first, sg.len, fwd, t.tix, blockIdx.x, pre, nxt, pass,
-			      out + sg.first, flags);
-}
-
-// the partitions' offsets (m + 1 of them) for fp_large_segments
-__global__ __launch_bounds__(256) void
-k_part_offsets(Starts part, uint64_t *off)
-{
-	for (BUN k = (BUN) blockIdx.x * blockDim.x + threadIdx.x; k <= part.m; k += (BUN) gridDim.x * blockDim.x)
-		off[k] = k < part.m ? part.at(k) : part.n;
-}
+};
 
 template <typename T1, typename T2>
 int
 run_fsum_par(const T1 *bv, const int8_t *o, BUN n, bool fwd, T2 *out, uint32_t *flags)
 {
-	hipStream_t st = stream();
-	const BUN nt = (n + RS_TILE - 1) / RS_TILE;
-	DevBuf tot(nt * sizeof(FSum<T2>)), pre(nt * sizeof(FSum<T2>)), fend(nt * sizeof(BUN)), nxt(nt * sizeof(BUN));
-	if (!tot.p || !pre.p || !fend.p || !nxt.p)
-		return -1;
-	if (nt > 0xffffffffull) {
-		seterr("42000!GDKanalyticalsum: too many rows on the device path\n");
-		return -1;
-	}
-	hipLaunchKernelGGL((k_rs_tile<T1, T2>), dim3((unsigned) nt), dim3(256), 0, st, bv, o, n, fwd,
-			   tot.as<FSum<T2>>(), fend.as<BUN>(), flags);
-	hipLaunchKernelGGL((k_rs_tiles<T2>), dim3(1), dim3(1024), 0, st, tot.as<FSum<T2>>(), fend.as<BUN>(), nt,
-			   pre.as<FSum<T2>>(), nxt.as<BUN>(), flags);
-	hipLaunchKernelGGL((k_rs_write<T1, T2>), dim3((unsigned) nt), dim3(256), 0, st, bv, o, n, fwd,
-			   pre.as<FSum<T2>>(), nxt.as<BUN>(), 0, out, flags);
-	hipLaunchKernelGGL((k_rs_write<T1, T2>), dim3((unsigned) nt), dim3(256), 0, st, bv, o, n, fwd,
-			   pre.as<FSum<T2>>(), nxt.as<BUN>(), 1, out, flags);
-	return sync() ? 0 : -1;
+	return rs_run_par(FSumScan<T1, T2>{bv}, o, n, fwd, out, flags);
 }
 
 // frames 3 / 4 over several partitions: the ones of at least par_min rows,
-// which the replay left out, in the parallel form -- the four passes over
-// the flat tile table of RS_TILE-position tiles that never straddle a
-// partition start
+// which the replay left out
 template <typename T1, typename T2>
 int
 run_fsum_large(const T1 *bv, const Starts &part, const int8_t *o, BUN n, BUN par_min, bool fwd, T2 *out,
 	       uint32_t *flags)
 {
-	hipStream_t st = stream();
 	ProfScope pseg("analyticalsum_fp_seg");
-	FpSegs ls;
-	DevBuf off((part.m + 1) * 8);
-	if (!off.p)
-		return -1;
-	hipLaunchKernelGGL(k_part_offsets, dim3(grid_for(part.m + 1, 1024, 1024)), dim3(256), 0, st, part,
-			   off.as<uint64_t>());
-	if (fp_large_segments(off.as<uint64_t>(), part.m, n, par_min, ls, RS_TILE) != 0 || ls.nseg == 0)
-		return -1;
-	const BUN nt = ls.ntile;
-	DevBuf tot(nt * sizeof(FSum<T2>)), pre(nt * sizeof(FSum<T2>)), fend(nt * sizeof(BUN)), nxt(nt * sizeof(BUN));
-	if (!tot.p || !pre.p || !fend.p || !nxt.p)
-		return -1;
-	const dim3 tg((unsigned) nt), tb(256);
-	hipLaunchKernelGGL((k_rs_tile_seg<T1, T2>), tg, tb, 0, st, bv, o, fwd, ls.segs, ls.tiles, tot.as<FSum<T2>>(),
-			   fend.as<BUN>(), flags);
-	hipLaunchKernelGGL((k_rs_tiles_seg<T2>), dim3((unsigned) ls.nseg), dim3(1024), 0, st, ls.segs, tot.as<FSum<T2>>(),
-			   fend.as<BUN>(), pre.as<FSum<T2>>(), nxt.as<BUN>(), flags);
-	hipLaunchKernelGGL((k_rs_write_seg<T1, T2>), tg, tb, 0, st, bv, o, fwd, ls.segs, ls.tiles, pre.as<FSum<T2>>(),
-			   nxt.as<BUN>(), 0, out, flags);
-	hipLaunchKernelGGL((k_rs_write_seg<T1, T2>), tg, tb, 0, st, bv, o, fwd, ls.segs, ls.tiles, pre.as<FSum<T2>>(),
-			   nxt.as<BUN>(), 1, out, flags);
-	return sync() ? 0 : -1;
+	return rs_run_large(FSumScan<T1, T2>{bv}, part, o, n, par_min, fwd, false, out, flags);
 }
 
 template <typename T1, typename T2>

@@ -10,7 +10,9 @@
 // order, per partition, in parallel over partitions and rows:
 //   * frames 3 / 4 / 5 (running and whole-partition): one lane per partition
 //     folds its rows forward (3, 5) or backward from the end (4) and writes
-//     each peer group's (or the partition's) result;
+//     each peer group's (or the partition's) result; a partition of at least
+//     fp_parallel_min() rows of the statistics takes the blocked scan of
+//     runscan.h instead (MomScan; rounding only);
 //   * frame 6: every row on its own;
 //   * every other frame: the reference's fanout-16 segment tree
 //     (gdk/gdk_analytic.h:63-130) for every partition at once -- one launch
@@ -25,6 +27,8 @@
 
 #include "mgdk_internal.h"
 #include "segments.h"
+#include "fpfold.h"
+#include "runscan.h"
 
 #pragma clang fp contract(off)
 
@@ -51,7 +55,7 @@ as_dbl<hge>(hge v)
 	return hge_to_dbl(v);
 }
 
-enum { K_VAR = 0, K_COV = 1, K_COR = 2 };
+enum { K_VAR = ST_VAR, K_COV = ST_COV, K_COR = ST_COR };
 
 // stdev_var_deltas / covariance_deltas / correlation_deltas
 // (gdk_analytic_statistics.c:794, :1081, :1320); op: K_VAR 0 stddev_samp
@@ -250,12 +254,19 @@ wflag(uint32_t *flags, uint32_t f)
 // partition): one lane per partition
 template <typename N>
 __global__ __launch_bounds__(64) void
-k_ws_replay(Cols c, Starts part, const int8_t *o, int frame, int op, typename N::Out *out, uint32_t *flags)
+k_ws_replay(Cols c, Starts part, const int8_t *o, int frame, int op, typename N::Out *out, uint32_t *flags,
+	    BUN par_min)
 {
 	const BUN k = (BUN) blockIdx.x * blockDim.x + threadIdx.x;
 	if (k >= part.m)
 		return;
 	const BUN ps = part.at(k), pe = part.end_of(k);
+	// a large partition is left to the parallel form (MomScan): flag bit 3
+	// tells the host that there is one
+	if (fp_large(pe - ps, par_min)) {
+		wflag(flags, 8);
+		return;
+	}
 	uint32_t f = 0;
 	N acc;
 	acc.zero();
@@ -312,6 +323,121 @@ k_ws_replay(Cols c, Starts part, const int8_t *o, int frame, int op, typename N:
 	}
 	wflag(flags, f);
 }
+
+// The parallel form of a large partition of the statistics
+// (fp_parallel_min): running moments as the blocked scan of runscan.h over
+// MomState merged by mom_comb, and WNode::result's step at the run ends.  An
+// accumulator that is not finite where a result is written is the overflow.
+// Only the rounding differs from the replay (DESIGN.md states the bound).
+template <typename T, int KIND>
+struct MomScan {
+	using State = MomState;
+	using Out = double;
+	static constexpr unsigned NC = KIND == K_VAR ? 1 : 2;
+	static constexpr unsigned TPT = 4;
+	// hge is staged as the double the fold takes (nil: NaN)
+	using SE = typename std::conditional<(sizeof(T) > 8), double, T>::type;
+	struct Raw {
+		SE v[NC];
+	};
+	struct Stage {
+		SE v[NC][RS_SLOTS];
+	};
+	const T *b1, *b2;
+	int op;
+	static __device__ __forceinline__ SE conv(T x)
+	{
+		if constexpr (sizeof(T) > 8)
+			return is_nil(x) ? __builtin_nan("") : as_dbl(x);
+		else
+			return x;
+	}
+	__device__ __forceinline__ void stage(Stage &sg, unsigned slot, BUN row) const
+	{
+		sg.v[0][slot] = conv(b1[row]);
+		if (NC == 2)
+			sg.v[NC - 1][slot] = conv(b2[row]);
+	}
+	__device__ __forceinline__ void stage_none(Stage &sg, unsigned slot) const
+	{
+		sg.v[0][slot] = (SE) 0;
+		if (NC == 2)
+			sg.v[NC - 1][slot] = (SE) 0;
+	}
+	__device__ __forceinline__ Raw raw(const Stage &sg, unsigned slot) const
+	{
+		Raw x;
+		x.v[0] = sg.v[0][slot];
+		if (NC == 2)
+			x.v[NC - 1] = sg.v[NC - 1][slot];
+		return x;
+	}
+	__device__ __forceinline__ State leaf(const Raw &x, bool valid) const
+	{
+		State s{0, 0, 0, 0, 0, 0};
+		if (!valid || is_nil(x.v[0]) || (NC == 2 && is_nil(x.v[NC - 1])))
+			return s;
+		s.n = 1;
+		s.mean1 = as_dbl(x.v[0]);
+		if (NC == 2)
+			s.mean2 = as_dbl(x.v[NC - 1]);
+		return s;
+	}
+	static __device__ __forceinline__ State zero() { return State{0, 0, 0, 0, 0, 0}; }
+	static __device__ __forceinline__ State comb(const State &a, const State &b, uint32_t &)
+	{
+		return mom_comb<KIND>(a, b);
+	}
+	static __device__ __forceinline__ State shfl_up(const State &v, int d)
+	{
+		State y{0, 0, 0, 0, 0, 0};
+		y.n = __shfl_up(v.n, d);
+		y.mean1 = __shfl_up(v.mean1, d);
+		y.m2 = __shfl_up(v.m2, d);
+		if (KIND != K_VAR)
+			y.mean2 = __shfl_up(v.mean2, d);
+		if (KIND == K_COR) {
+			y.down1 = __shfl_up(v.down1, d);
+			y.down2 = __shfl_up(v.down2, d);
+		}
+		return y;
+	}
+	__device__ __forceinline__ Out result(const State &s, bool end, uint32_t &fl) const
+	{
+		if (!end)
+			return 0;
+		const double nil = __builtin_nan("");
+		if (!__builtin_isfinite(s.m2) ||
+		    (KIND == K_COR && (!__builtin_isfinite(s.down1) || !__builtin_isfinite(s.down2)))) {
+			fl |= 1;
+			return nil;
+		}
+		if (KIND == K_COR) {
+			if (s.n != 0 && s.down1 != 0 && s.down2 != 0)
+				return (s.m2 / s.n) / (sqrt(s.down1 / s.n) * sqrt(s.down2 / s.n));
+			fl |= 2;
+			return nil;
+		}
+		const double sample = (KIND == K_VAR ? (op & 1) == 0 : op == 0) ? 1 : 0;
+		if (s.n > sample) {
+			const double v = s.m2 / (s.n - sample);
+			return KIND == K_VAR && op < 2 ? sqrt(v) : v;
+		}
+		fl |= 2;
+		return nil;
+	}
+};
+
+// the scan of a window function's node: only the statistics have one
+template <typename N>
+struct ScanOf {
+	static constexpr bool has = false;
+};
+template <typename T, int KIND>
+struct ScanOf<WNode<T, KIND>> {
+	static constexpr bool has = true;
+	using P = MomScan<T, KIND>;
+};
 
 // frame 6 of the products: each row's own value in the result type
 template <typename N>
@@ -468,6 +594,8 @@ ws_run(mgdk_bat *r, mgdk_bat *p, mgdk_bat *o, mgdk_bat *b1, mgdk_bat *b2, mgdk_b
 		return -1;
 	mgdk_bat *Sp = nullptr;
 	int rc = -1;
+	Starts part{};
+	BUN par_min = MGDK_BUN_NONE;
 	if (frame_type == 6) {
 		if (stat) {
 			// the row alone: 0 (population) or nil, whatever the value
@@ -482,13 +610,16 @@ ws_run(mgdk_bat *r, mgdk_bat *p, mgdk_bat *o, mgdk_bat *b1, mgdk_bat *b2, mgdk_b
 					   fl.as<uint32_t>());
 		}
 	} else {
-		Starts part;
 		if (make_starts(p ? (const int8_t *) p->theap : nullptr, n, part, &Sp) < 0)
 			goto out;
 		if (frame_type >= 3 && frame_type <= 5) {
+			// (the statistics' partitions of at least fp_parallel_min() rows
+			// are left to rs_run_large below)
+			if (ScanOf<N>::has && n >= fp_parallel_min())
+				par_min = fp_parallel_min();
 			hipLaunchKernelGGL((k_ws_replay<N>), dim3((unsigned) ((part.m + 63) / 64)), dim3(64), 0, st, c, part,
 					   frame_type == 5 ? (const int8_t *) nullptr : (const int8_t *) o->theap, frame_type,
-					   op, out, fl.as<uint32_t>());
+					   op, out, fl.as<uint32_t>(), par_min);
 		} else {
 			if (n >= 0xffffffffull) {
 				seterr("42000!analytic: more than 2^32-1 rows on the device path\n");
@@ -534,6 +665,18 @@ ws_run(mgdk_bat *r, mgdk_bat *p, mgdk_bat *o, mgdk_bat *b1, mgdk_bat *b2, mgdk_b
 		uint32_t *h = (uint32_t *) pinned(16);
 		if (!hip_ok(hipMemcpyAsync(h, fl.p, 4, hipMemcpyDeviceToHost, st), "memcpy") || !sync())
 			goto out;
+		if constexpr (ScanOf<N>::has) {
+			if (h[0] & 8) {
+				// the replay of frames 3 / 4 / 5 left large partitions out
+				ProfScope pseg("analytic_stats_fp_seg");
+				using P = typename ScanOf<N>::P;
+				const P sc{(decltype(P::b1)) b1->theap, (decltype(P::b2)) (b2 ? b2->theap : nullptr), op};
+				if (rs_run_large(sc, part, frame_type == 5 ? (const int8_t *) nullptr : (const int8_t *) o->theap, n,
+						 par_min, frame_type != 4, frame_type == 5, out, fl.as<uint32_t>()) < 0 ||
+				    !hip_ok(hipMemcpyAsync(h, fl.p, 4, hipMemcpyDeviceToHost, st), "memcpy") || !sync())
+					goto out;
+			}
+		}
 		if (h[0] & 1) {
 			seterr("22003!overflow in calculation.\n");
 			goto out;

@@ -25,6 +25,7 @@
 // groups (mgdk_BATsort, both on the device); one lane per run of equal group
 // ids then picks its quantile position -- or interpolates (the _avg forms).
 #include "mgdk_internal.h"
+#include "fpfold.h"
 
 #include <cmath>
 #include <string>
@@ -48,7 +49,6 @@ to_dbl<hge>(hge v)
 	return hge_to_dbl(v);
 }
 
-enum { ST_VAR = 0, ST_COV = 1, ST_COR = 2 };
 constexpr unsigned long long CNT_NONE = ~0ull;
 
 // flags: bit 0 overflow ("22003!overflow in calculation."), bit 1 a nil result
@@ -435,44 +435,7 @@ group_moments(const char *fn, int kind, mgdk_bat *b1, mgdk_bat *b2, mgdk_bat *g,
 // LeVeque (n = na + nb, d = mean_b - mean_a: mean = mean_a + d nb / n,
 // M2 = M2a + M2b + d^2 na nb / n, the co-moments alike).  Only the rounding
 // differs from the sequential fold (DESIGN.md states the bound).
-struct MomState {
-	double n, mean1, mean2, m2, down1, down2;   // m2: the co-moment (up) for ST_COR
-};
-
-template <int KIND>
-__device__ __forceinline__ MomState
-mom_comb(const MomState &a, const MomState &b)
-{
-	if (a.n == 0)
-		return b;
-	if (b.n == 0)
-		return a;
-	MomState r;
-	r.n = a.n + b.n;
-	const double f = b.n / r.n, d1 = b.mean1 - a.mean1, w = a.n * f;
-	r.mean1 = a.mean1 + d1 * f;
-	r.mean2 = r.down1 = r.down2 = 0;
-	if (KIND == ST_VAR) {
-		r.m2 = a.m2 + b.m2 + d1 * d1 * w;
-	} else {
-		const double d2 = b.mean2 - a.mean2;
-		r.mean2 = a.mean2 + d2 * f;
-		r.m2 = a.m2 + b.m2 + d1 * d2 * w;
-		if (KIND == ST_COR) {
-			r.down1 = a.down1 + b.down1 + d1 * d1 * w;
-			r.down2 = a.down2 + b.down2 + d2 * d2 * w;
-		}
-	}
-	return r;
-}
-
-template <int KIND>
-__device__ __forceinline__ bool
-mom_inf(const MomState &s)
-{
-	return __builtin_isinf(s.m2) || (KIND == ST_COR && (__builtin_isinf(s.down1) || __builtin_isinf(s.down2)));
-}
-
+// (MomState, mom_comb, mom_inf: fpfold.h)
 template <typename T, int KIND>
 __global__ __launch_bounds__(256) void
 k_mom_par(const T *v1, const T *v2, BUN n, BUN tile, MomState *part, uint32_t *flags)

@@ -11,6 +11,11 @@ groups, the running dbl SUM over K contiguous partitions, replay against
 parallel.  --small-groups G times the grouped average and stdev over G
 small groups (none reaches the threshold) at the default knob; --reps N
 sets the timed repetitions.  A trailing "par" skips the replay legs.
+
+--window {avg,stddev_samp,correlation} adds that window function over the
+same partitions (peer groups of 16 rows) beside the running SUM, for --frame
+{3,4,5} (default 3; the running SUM stays frame 3 / 4), with every timed
+repetition listed ("samples_ms").
 """
 import argparse
 import json
@@ -36,7 +41,18 @@ def timed(fn, reps):
     return out, (time.perf_counter() - t) / reps * 1e3
 
 
-def segments(n, ngroups, nparts, nsmall, par_only, reps):
+def samples(fn, reps):
+    """each of reps further calls on its own, in ms"""
+    ms = []
+    for _ in range(reps):
+        t = time.perf_counter()
+        fn()
+        gdk.sync()
+        ms.append(round((time.perf_counter() - t) * 1e3, 3))
+    return ms
+
+
+def segments(n, ngroups, nparts, nsmall, par_only, reps, window=None, frame=3):
     """replay against parallel over several equal groups / partitions"""
     gdk.init(0)
     r = np.random.default_rng(5)
@@ -57,11 +73,23 @@ def segments(n, ngroups, nparts, nsmall, par_only, reps):
         o = p.copy()
         o[::16] = 1                   # peer groups of 16 rows
         P, O = gdk.BAT.from_numpy(gdk.TYPE_bit, p), gdk.BAT.from_numpy(gdk.TYPE_bit, o)
-        ops["running_sum_%d_partitions" % nparts] = lambda: gdk.GDKanalyticalsum(B, P, O, None, None, gdk.TYPE_dbl, 3)
+        ops["running_sum_%d_partitions" % nparts] = lambda: gdk.GDKanalyticalsum(B, P, O, None, None, gdk.TYPE_dbl,
+                                                                                 4 if frame == 4 else 3)
+        wtag = "window_%s_frame%d_%d_partitions" % (window, frame, nparts)
+        if window == "avg":
+            ops[wtag] = lambda: gdk.GDKanalyticalavg(B, P, O, None, None, frame)
+        elif window == "stddev_samp":
+            ops[wtag] = lambda: gdk.GDKanalytical_stat(window, B, None, P, O, None, None, frame)
+        elif window == "correlation":
+            y = 0.5 * x + (r.standard_normal(n) * 100.0 + 50.0) * 0.3
+            B2 = gdk.BAT.from_numpy(gdk.TYPE_dbl, y, sorted_=False, revsorted=False, key=False)
+            ops[wtag] = lambda: gdk.GDKanalytical_stat(window, B, B2, P, O, None, None, frame)
     res = {"rows": n}
     for name, dev in ops.items():
         par, ms_par = timed(dev, reps)
         d = {"parallel_ms" if not nsmall else "ms": round(ms_par, 3)}
+        if window:
+            d["samples_ms"] = samples(dev, reps)
         if not par_only and not nsmall:
             prev = gdk.set_fp_parallel_min(None)
             try:
@@ -85,11 +113,16 @@ def main():
     ap.add_argument("--partitions", nargs="?", type=int, const=4, default=0)
     ap.add_argument("--small-groups", type=int, default=0)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--window", choices=["avg", "stddev_samp", "correlation"])
+    ap.add_argument("--frame", type=int, choices=[3, 4, 5], default=3)
     args = ap.parse_args()
     n = args.rows
     par_only = args.par == "par"     # profiling runs: no replay, no oracle
+    if args.window and not args.partitions:
+        args.partitions = 4
     if args.groups or args.partitions or args.small_groups:
-        segments(n, 0 if args.small_groups else args.groups, args.partitions, args.small_groups, par_only, args.reps)
+        segments(n, 0 if args.small_groups else args.groups, args.partitions, args.small_groups, par_only, args.reps,
+                 args.window, args.frame)
         return
     ns = min(n, 10_000_000)
     gdk.init(0)
