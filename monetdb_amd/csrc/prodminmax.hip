@@ -559,6 +559,12 @@ struct ProdArgs {
 	oid off;
 	const uint32_t *perm;          // rows grouped by group (nullptr: rows in order)
 	const uint64_t *start;         // group k: [start[k], start[k+1]) (nullptr: one group of n)
+	const oid *gids;               // the rows' group ids (nullptr: dense from gseq)
+	oid gseq, gmin;
+	// set by the grouped call: with start == nullptr only the rows with an id
+	// in [gmin, gmin + ngrp) are the group's.  BATprod's one-lane float call
+	// has no ids and leaves it false: that call is why the flag exists
+	bool check_ids;
 	BUN ngrp, n;
 	bool skip_nils, nil_if_empty;
 	void *res;
@@ -655,7 +661,15 @@ k_prod(const T1 *v, ProdArgs a)
 	bool seen = false, ovf = false;
 	for (BUN j = j0; j < j1 && !ovf; j++) {
 		const BUN r = a.perm ? a.perm[j] : j;
+		// the value is loaded ahead of the id check (every candidate row is
+		// in bounds), so the two loads of a row are in flight together
 		const T1 x = v[a.off + r];
+		if (!a.start && a.check_ids) {
+			// one group: every candidate row, its id range-checked
+			const oid g = a.gids ? a.gids[r] : a.gseq + r;
+			if (g < a.gmin || g - a.gmin >= a.ngrp)
+				continue;
+		}
 		if (KIND == PK_HGE && a.nil_if_empty && !seen) {
 			seen = true;
 			prod = 1;
@@ -1148,8 +1162,6 @@ mgdk_BATgroupprod(mgdk_bat *b, mgdk_bat *g, mgdk_bat *e, mgdk_bat *s, int tp, bo
 	Cand ci0;
 	if (cand_init(&ci0, b, s) < 0)
 		return nullptr;
-	const BUN cnt1 = b->count;
-	const oid hseq1 = b->hseqbase;
 	mgdk_bat *v1 = b;
 	AggrInit a;
 	if (group_init(&a, &v1, g, e, s) < 0)
@@ -1164,8 +1176,6 @@ mgdk_BATgroupprod(mgdk_bat *b, mgdk_bat *g, mgdk_bat *e, mgdk_bat *s, int tp, bo
 			    (g->ttype == MGDK_oid && g->tseqbase != MGDK_OID_NIL);
 	if ((e == nullptr || (e->count == ci0.n && e->hseqbase == ci0.seq)) && (gdense || (g->tkey && g->tnonil))) {
 		// singleton groups: BATconvert(b, s, tp, 0, 0, 0)
-		(void) cnt1;
-		(void) hseq1;
 		return mgdk_BATconvert(b, s, tp, 0, 0, 0);
 	}
 	int kind;
@@ -1188,6 +1198,10 @@ mgdk_BATgroupprod(mgdk_bat *b, mgdk_bat *g, mgdk_bat *e, mgdk_bat *s, int tp, bo
 	pa.off = a.ci.seq - v1->hseqbase;
 	pa.perm = gr.perm;
 	pa.start = gr.start_p;
+	pa.gids = a.gids;
+	pa.gseq = a.gseq;
+	pa.gmin = a.min;
+	pa.check_ids = true;
 	pa.ngrp = ng;
 	pa.n = a.ci.n;
 	pa.skip_nils = skip_nils;

@@ -1630,6 +1630,13 @@ ora_groupprod(const ora_bat *b, const ora_bat *g, const ora_bat *e, const ora_ba
 	aggr_ctx a;
 	if (aggr_init(&a, b, g, e, s) < 0)
 		return NULL;
+	/* singleton groups (gdk_aggr.c:1604-1611, ahead of doprod and its type
+	 * check): g dense or key + nonil and e absent or aligned -- every result
+	 * is its row's value in the result type, a nil row nil whatever
+	 * skip_nils says */
+	if (a.ci.n && a.ngrp && (e == NULL || (e->count == a.ci.n && e->hseqbase == b->hseqbase)) &&
+	    (g->tseqbase != ORA_OID_NIL || (g->key && g->nonil)))
+		return ora_convert(b, s, tp, 0, 0, 0);
 	const int kind = prod_kind(b->type, tp);
 	if (kind < 0 && a.ci.n && a.ngrp) {
 		ora_seterr("type combination (prod) not supported");
@@ -1658,7 +1665,9 @@ ora_groupprod(const ora_bat *b, const ora_bat *g, const ora_bat *e, const ora_ba
 	uint64_t nils = 0;
 	for (uint64_t k = 0; k < a.ngrp; k++) {
 		prod_put(tp, bn->base, k, &st[k]);
-		nils += st[k].nil;
+		/* 0 * inf leaves a NaN, which is the nil of flt / dbl: the nil /
+		 * nonil properties describe the values the result holds */
+		nils += st[k].nil || (kind == 2 && isnan(st[k].fp));
 	}
 	free(st);
 	bn->sorted = bn->revsorted = bn->key = a.ngrp <= 1;
