@@ -594,6 +594,25 @@ int mgdk_GDKanalyticalprod(mgdk_bat *r, mgdk_bat *p, mgdk_bat *o, mgdk_bat *b, m
 			   int tp2, int frame_type);
 int mgdk_GDKanalyticalavginteger(mgdk_bat *r, mgdk_bat *p, mgdk_bat *o, mgdk_bat *b, mgdk_bat *s, mgdk_bat *e,
 				 int tpe, int frame_type);
+/* sql/backends/monet5/sql_rank.c SQLrow_number, SQLrank, SQLdense_rank,
+ * SQLpercent_rank, SQLcume_dist: the loop bodies over the partition bits p
+ * and peer bits o (the results of GDKanalyticaldiff).  b gives only count
+ * and hseqbase (any type, void and str included); p / o: bit BATs of at
+ * least count(b) rows, or NULL for the MAL call's scalar bit (no PARTITION
+ * BY / no ORDER BY).  A non-zero byte is a set bit (the nil -128 included);
+ * row 0 starts a partition and a peer group whatever p[0] and o[0] hold.
+ * The result is a NEW BAT with b's hseqbase and count, tnonil: int for
+ * row_number (1, 2, ... in the partition), rank (the row_number of the peer
+ * group's first row) and dense_rank (1 + the peer groups before the row's in
+ * the partition); dbl for percent_rank ((rank - 1) / (rows of the partition
+ * - 1), 0 for a one-row partition) and cume_dist (rows up to the end of the
+ * peer group / rows of the partition), each one IEEE division.  More than
+ * 2^31 - 1 rows are refused (the reference's int counters wrap there). */
+mgdk_bat *mgdk_SQLrow_number(mgdk_bat *b, mgdk_bat *p);
+mgdk_bat *mgdk_SQLrank(mgdk_bat *b, mgdk_bat *p, mgdk_bat *o);
+mgdk_bat *mgdk_SQLdense_rank(mgdk_bat *b, mgdk_bat *p, mgdk_bat *o);
+mgdk_bat *mgdk_SQLpercent_rank(mgdk_bat *b, mgdk_bat *p, mgdk_bat *o);
+mgdk_bat *mgdk_SQLcume_dist(mgdk_bat *b, mgdk_bat *p, mgdk_bat *o);
 
 /* ---- compressed column inputs (sql/backends/monet5/dict.c, for.c):
  *      a DICT column is codes o (bte/sht/int, read unsigned) + the

@@ -28,6 +28,18 @@
 
 using namespace mgdk;
 
+// a partition / peer column: NULL or a bit BAT of n rows (longer_ok: at
+// least n); declared in segments.h
+bool
+mgdk::bits_ok(mgdk_bat *p, BUN n, bool longer_ok)
+{
+	if (p && ((longer_ok ? p->count < n : p->count != n) || width_of(p->ttype) != 1)) {
+		seterr("analytic: p and o must be bit BATs aligned with b");
+		return false;
+	}
+	return true;
+}
+
 namespace {
 
 // peer-group starts: row 0, a partition start or a peer start
@@ -464,16 +476,6 @@ is_nil_val(int cls, const void *v)
 	case -4: { float f; memcpy(&f, v, 4); return f != f; }
 	default: { double d; memcpy(&d, v, 8); return d != d; }
 	}
-}
-
-bool
-bits_ok(mgdk_bat *p, BUN n)
-{
-	if (p && (p->count != n || width_of(p->ttype) != 1)) {
-		seterr("analytic: p and o must be bit BATs aligned with b");
-		return false;
-	}
-	return true;
 }
 
 int

@@ -59,4 +59,8 @@ struct Starts {
 // *keep owns the compacted list (unfix it after the kernels that read it)
 int make_starts(const int8_t *flags, BUN n, Starts &st, mgdk_bat **keep);
 
+// a partition / peer column of a window function over n rows: NULL or a bit
+// BAT of n rows (longer_ok: of at least n); sets the error otherwise
+bool bits_ok(mgdk_bat *p, BUN n, bool longer_ok = false);
+
 }  // namespace mgdk

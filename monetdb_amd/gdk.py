@@ -266,6 +266,11 @@ _SIGS = {
     "mgdk_GDKanalytical_covariance_pop": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int]),
     "mgdk_GDKanalytical_correlation": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int]),
     "mgdk_GDKanalyticalprod": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_int]),
+    "mgdk_SQLrow_number": (P, [C.c_void_p] * 2),
+    "mgdk_SQLrank": (P, [C.c_void_p] * 3),
+    "mgdk_SQLdense_rank": (P, [C.c_void_p] * 3),
+    "mgdk_SQLpercent_rank": (P, [C.c_void_p] * 3),
+    "mgdk_SQLcume_dist": (P, [C.c_void_p] * 3),
     "mgdk_BATlowerbound2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                       C.c_void_p]),
     "mgdk_BATupload_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
@@ -1162,6 +1167,36 @@ def GDKanalyticalntile(b, p, n=None, ntile=None, tpe=None):
     _chk(lib().mgdk_GDKanalyticalntile(r.ptr, b.ptr, _p(p), _p(n), tpe,
                                        _valptr(tpe, ntile, keep) if n is None else None))
     return r
+
+
+def SQLrow_number(b, p=None):
+    """sql_rank.c SQLrow_number: 1, 2, ... within the row's partition (int).
+    p: the partition bits of GDKanalyticaldiff, None: one partition."""
+    return BAT(lib().mgdk_SQLrow_number(b.ptr, _p(p)))
+
+
+def SQLrank(b, p=None, o=None):
+    """sql_rank.c SQLrank: the row_number of the first row of the row's
+    peer group (int).  o: the peer bits, None: no ORDER BY."""
+    return BAT(lib().mgdk_SQLrank(b.ptr, _p(p), _p(o)))
+
+
+def SQLdense_rank(b, p=None, o=None):
+    """sql_rank.c SQLdense_rank: 1 + the peer groups before the row's in
+    its partition (int)."""
+    return BAT(lib().mgdk_SQLdense_rank(b.ptr, _p(p), _p(o)))
+
+
+def SQLpercent_rank(b, p=None, o=None):
+    """sql_rank.c SQLpercent_rank: (rank - 1) / (partition rows - 1), 0 in
+    a one-row partition (dbl)."""
+    return BAT(lib().mgdk_SQLpercent_rank(b.ptr, _p(p), _p(o)))
+
+
+def SQLcume_dist(b, p=None, o=None):
+    """sql_rank.c SQLcume_dist: the rows up to the end of the row's peer
+    group over the partition's rows (dbl)."""
+    return BAT(lib().mgdk_SQLcume_dist(b.ptr, _p(p), _p(o)))
 
 
 def GDKanalyticalfirst(b, s, e):
