@@ -6,8 +6,9 @@
 // and independent of arrival order -- results are bitwise reproducible).
 // The reference checks overflow after every add (ADDI_WITH_CHECK,
 // gdk/gdk_aggr.c:429-705); a prefix can only leave the result type's range
-// if count * max|v| exceeds it, which the kernel also measures; only then a
-// one-workgroup ordered pass re-evaluates the prefixes to decide exactly.
+// if count * max|v| exceeds it (per group for the grouped sum), which the
+// kernels also measure; only then an ordered pass re-evaluates the prefixes
+// to decide exactly (k_sum_ordered, k_gsum_ordered).
 //   BATsum       gdk/gdk_aggr.c:1018 (dosum :708; int->dbl via BATcalcavg :1112-1156)
 //   BATgroupsum  :900 (nil_if_empty; the "nil before first value" rule :497-527)
 //   BATgroupcount :3069, BATgroupavg3 :1996 (rounding :2070-2095),
@@ -152,69 +153,146 @@ k_sum_fin(const SumPart *parts, uint32_t np, SumOut *o)
 	}
 }
 
-// ordered prefix check for the rare case where overflow is possible: one
-// workgroup, each lane a contiguous chunk, then an ordered combine of
-// (sum, max prefix, min prefix).  Uses a 192-bit-safe formulation: values are
-// at most 128 bits and we stop at the first overflow, so partial sums are
-// kept as (hi: int64 guard, 128-bit) via a per-chunk scan.
+// ---- the exact, ordered overflow decision ----------------------------------
+// A signed 192-bit integer (w2 * 2^128 + w1 * 2^64 + w0): values are at most
+// 128 bits and a call has fewer than 2^64 rows, so no running sum wraps.
+struct I192 {
+	unsigned long long w0, w1;
+	long long w2;
+};
+
+__device__ __forceinline__ I192
+i192(hge v)
+{
+	return I192{(unsigned long long) (uhge) v, (unsigned long long) ((uhge) v >> 64), v < 0 ? -1ll : 0ll};
+}
+
+__device__ __forceinline__ uhge
+lo192(const I192 &a)
+{
+	return ((uhge) a.w1 << 64) | a.w0;
+}
+
+__device__ __forceinline__ I192
+add192(const I192 &a, const I192 &b)
+{
+	const uhge la = lo192(a), lo = la + lo192(b);
+	return I192{(unsigned long long) lo, (unsigned long long) (lo >> 64), a.w2 + b.w2 + (lo < la ? 1 : 0)};
+}
+
+__device__ __forceinline__ bool
+lt192(const I192 &a, const I192 &b)
+{
+	return a.w2 != b.w2 ? a.w2 < b.w2 : lo192(a) < lo192(b);
+}
+
+// outside [-max, max] (max > 0: the nil value -max - 1 is outside)
+__device__ __forceinline__ bool
+out192(const I192 &x, hge max)
+{
+	if (x.w2 == 0)
+		return lo192(x) > (uhge) max;
+	if (x.w2 == -1)
+		return lo192(x) < (uhge) 0 - (uhge) max;
+	return true;
+}
+
+// a run of values in candidate order: its sum and the largest and smallest
+// of its running sums.  pfx_cat is associative, so a run may be cut into
+// pieces that are folded separately and joined in order.
+struct Pfx {
+	I192 s, mx, mn;
+	int has;
+};
+
+__device__ __forceinline__ void
+pfx_add(Pfx &p, hge v)
+{
+	p.s = add192(p.s, i192(v));
+	if (!p.has) {
+		p.mx = p.mn = p.s;
+		p.has = 1;
+	} else {
+		if (lt192(p.mx, p.s))
+			p.mx = p.s;
+		if (lt192(p.s, p.mn))
+			p.mn = p.s;
+	}
+}
+
+__device__ __forceinline__ Pfx
+pfx_cat(const Pfx &a, const Pfx &b)
+{
+	if (!b.has)
+		return a;
+	if (!a.has)
+		return b;
+	Pfx r;
+	r.has = 1;
+	r.s = add192(a.s, b.s);
+	const I192 bx = add192(a.s, b.mx), bn = add192(a.s, b.mn);
+	r.mx = lt192(a.mx, bx) ? bx : a.mx;
+	r.mn = lt192(bn, a.mn) ? bn : a.mn;
+	return r;
+}
+
+// the 256 lanes' runs joined in lane order (an in-order tree in LDS);
+// true in thread 0 when a running sum left [-max, max]
+__device__ __forceinline__ bool
+pfx_block_over(const Pfx &mine, hge max)
+{
+	// word by word, so that the runs stay in registers (copying the struct
+	// through LDS went through scratch memory)
+	__shared__ unsigned long long s_w[9][256];
+	__shared__ int s_has[256];
+	auto put = [&](unsigned t, const Pfx &p) {
+		s_w[0][t] = p.s.w0, s_w[1][t] = p.s.w1, s_w[2][t] = (unsigned long long) p.s.w2;
+		s_w[3][t] = p.mx.w0, s_w[4][t] = p.mx.w1, s_w[5][t] = (unsigned long long) p.mx.w2;
+		s_w[6][t] = p.mn.w0, s_w[7][t] = p.mn.w1, s_w[8][t] = (unsigned long long) p.mn.w2;
+		s_has[t] = p.has;
+	};
+	auto get = [&](unsigned t) {
+		Pfx p;
+		p.s = I192{s_w[0][t], s_w[1][t], (long long) s_w[2][t]};
+		p.mx = I192{s_w[3][t], s_w[4][t], (long long) s_w[5][t]};
+		p.mn = I192{s_w[6][t], s_w[7][t], (long long) s_w[8][t]};
+		p.has = s_has[t];
+		return p;
+	};
+	__syncthreads();                 // the words may still be read by a previous call
+	put(threadIdx.x, mine);
+	__syncthreads();
+	for (unsigned d = 1; d < 256; d <<= 1) {
+		if ((threadIdx.x & (2 * d - 1)) == 0)
+			put(threadIdx.x, pfx_cat(get(threadIdx.x), get(threadIdx.x + d)));
+		__syncthreads();
+	}
+	if (threadIdx.x != 0)
+		return false;
+	const Pfx t = get(0);
+	return t.has && (out192(t.mx, max) || out192(t.mn, max));
+}
+
+// ordered prefix check of BATsum for the rare case where overflow is
+// possible: one workgroup, each lane a contiguous chunk of the rows before
+// the first nil that counts, then the chunks joined in order
 __global__ __launch_bounds__(256) void
 k_sum_ordered(const void *base, int w, bool dense, oid off, const oid *oids, oid hseq, BUN n,
 	      hge max, unsigned long long *ovf)
 {
-	__shared__ hge s_sum[256], s_mx[256], s_mn[256];
-	__shared__ int s_has[256], s_bad[256];
 	const BUN chunk = (n + 255) / 256;
-	const BUN a = threadIdx.x * chunk, e = a + chunk < n ? a + chunk : n;
-	hge s = 0, mx = 0, mn = 0;
-	int has = 0, bad = 0;
+	const BUN a = threadIdx.x * chunk < n ? threadIdx.x * chunk : n, e = a + chunk < n ? a + chunk : n;
+	Pfx p{};
 	for (BUN i = a; i < e; i++) {
-		BUN p = dense ? off + i : oids[i] - hseq;
+		BUN pos = dense ? off + i : oids[i] - hseq;
 		bool isnil;
-		hge v = ldv(base, w, p, isnil);
-		if (isnil)
-			continue;
-		uhge r = (uhge) s + (uhge) v;
-		hge rs = (hge) r;
-		if (((s < 0) == (v < 0)) && ((rs < 0) != (s < 0)))
-			bad = 1;   // the chunk's own running sum left 128 bits: overflow for sure
-		s = rs;
-		if (!has) { mx = mn = s; has = 1; }
-		else { mx = s > mx ? s : mx; mn = s < mn ? s : mn; }
+		hge v = ldv(base, w, pos, isnil);
+		if (!isnil)
+			pfx_add(p, v);
 	}
-	s_sum[threadIdx.x] = s;
-	s_mx[threadIdx.x] = mx;
-	s_mn[threadIdx.x] = mn;
-	s_has[threadIdx.x] = has;
-	s_bad[threadIdx.x] = bad;
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		// chunk-local overflow of the 128-bit running sum only matters if
-		// the true prefix also overflows, which it then does: any chunk
-		// prefix beyond 2^127 plus a prefix sum below max is beyond max?
-		// Not in general -- combine exactly with a 192-bit accumulator.
-		__int128 acc_lo = 0;
-		long long acc_hi = 0;   // acc = acc_hi * 2^128 + (uhge) acc_lo, signed
-		bool over = false;
-		for (int t = 0; t < 256 && !over; t++) {
-			if (s_bad[t]) { over = true; break; }
-			if (!s_has[t])
-				continue;
-			// test base + mx and base + mn against [-max, max]
-			for (int q = 0; q < 2 && !over; q++) {
-				hge x = q ? s_mn[t] : s_mx[t];
-				uhge lo = (uhge) acc_lo + (uhge) x;
-				long long hi = acc_hi + ((lo < (uhge) acc_lo) ? 1 : 0) + (x < 0 ? -1 : 0);
-				// value = hi*2^128 + lo (lo unsigned)
-				if (hi == 0 && (hge) lo >= 0) { if ((hge) lo > max) over = true; }
-				else if (hi == -1 && (hge) lo < 0) { if ((hge) lo < -max) over = true; }
-				else over = true;
-			}
-			uhge lo = (uhge) acc_lo + (uhge) s_sum[t];
-			acc_hi = acc_hi + ((lo < (uhge) acc_lo) ? 1 : 0) + (s_sum[t] < 0 ? -1 : 0);
-			acc_lo = (hge) lo;
-		}
+	const bool over = pfx_block_over(p, max);
+	if (threadIdx.x == 0)
 		*ovf = over ? 1 : 0;
-	}
 }
 
 hge
@@ -257,6 +335,22 @@ mag_bound(unsigned long long cls)
 	if (cls >> 63)
 		return ldexpl((long double) ((cls & ~(1ull << 63)) + 1), 64);
 	return ((long double) cls + 1) * 2;
+}
+
+// the same bound in exact integers (at most 2^127), and the gate of the
+// ordered decisions: can cnt values of that magnitude leave [-max, max]?
+uhge
+mag_bound_u(unsigned long long cls)
+{
+	if (cls >> 63)
+		return (uhge) ((cls & ~(1ull << 63)) + 1) << 64;
+	return ((uhge) cls + 1) * 2;
+}
+
+bool
+sum_may_overflow(unsigned long long cnt, unsigned long long cls, hge max)
+{
+	return cnt != 0 && mag_bound_u(cls) > (uhge) max / cnt;
 }
 
 }  // namespace
@@ -334,9 +428,7 @@ mgdk_BATsum(void *res, int tp, mgdk_bat *b, mgdk_bat *s, bool skip_nils, bool ni
 	const hge max = tmax(tp);
 	const BUN firstnil = (!skip_nils && h->firstnil != ~0ull) ? h->firstnil : ci.n;
 	// could any prefix within [0, firstnil) leave [-max, max]?
-	long double bound = mag_bound(h->maxabs) * (long double) cnt;
-	bool maybe = bound > (long double) max;
-	if (maybe) {
+	if (sum_may_overflow(cnt, h->maxabs, max)) {
 		unsigned long long *ov = (unsigned long long *) o;
 		hipLaunchKernelGGL(k_sum_ordered, dim3(1), dim3(256), 0, stream(), b->theap, b->twidth, ci.dense, off,
 				   ci.oids, b->hseqbase, firstnil, max, ov);
@@ -793,6 +885,17 @@ struct SOut {
 	hge max;
 	uint32_t *flags;
 	bool on;
+	unsigned long long *cmax;   // the largest group's number of values (see GFlags)
+};
+
+// what BATgroupsum's kernels leave for the host, read in one copy: the flag
+// word (bit 0: a group's final sum beyond the result type, bit 1: a nil
+// result), the largest number of values in one group and the magnitude class
+// of the values.  A running sum can leave the range only in a group with
+// count * bound(class) > max; only then the ordered decision runs.
+struct GFlags {
+	uint32_t flags, pad;
+	unsigned long long cmax, maxabs;
 };
 
 struct GEdge {
@@ -801,10 +904,11 @@ struct GEdge {
 };
 
 __device__ __forceinline__ uint32_t
-sout_put(const SOut &so, BUN gi, uhge s, unsigned long long c)
+sout_put(const SOut &so, BUN gi, uhge s, unsigned long long c, unsigned long long &cmax)
 {
 	const hge sv = (hge) s;
 	const bool nil = c == 0;
+	cmax = c > cmax ? c : cmax;
 	put_res_d(so.out, so.bt, gi, nil ? 0 : sv, nil);
 	return (sv > so.max || sv < -so.max ? 1u : 0u) | (nil ? 2u : 0u);
 }
@@ -860,9 +964,10 @@ k_gaggr_sorted(const void *base, oid off, const oid *gids, oid gseq, oid gmin, B
 	unsigned long long mxa = 0;
 	oid sbase = 0, send = 0;     // staged ids: (sbase, send)
 	uint32_t sof = 0;            // SOut flags
+	unsigned long long scm = 0;  // SOut: most values in one group
 	auto flush = [&](bool atomic, BUN gi, const GRun &r) {
 		if (!atomic && so.on && !(STAGE && stage && gi + gmin > sbase && gi + gmin < send)) {
-			sof |= sout_put(so, gi, r.s, r.c);
+			sof |= sout_put(so, gi, r.s, r.c, scm);
 			return;
 		}
 		if (STAGE && stage && !atomic && gi + gmin > sbase && gi + gmin < send) {
@@ -1125,7 +1230,7 @@ k_gaggr_sorted(const void *base, oid off, const oid *gids, oid gseq, oid gmin, B
 			for (oid h = lo + lane; h < hi; h += 64) {
 				const BUN k = h - sbase, gi = h - gmin;
 				if (so.on) {
-					sof |= sout_put(so, gi, ((uhge) s_hi[k] << 64) | s_lo[k], s_c[k]);
+					sof |= sout_put(so, gi, ((uhge) s_hi[k] << 64) | s_lo[k], s_c[k], scm);
 					continue;
 				}
 				if (do_sum)
@@ -1142,10 +1247,18 @@ k_gaggr_sorted(const void *base, oid off, const oid *gids, oid gseq, oid gmin, B
 	if (lane == 0 && mxa)
 		publish_max(maxabs, mxa);
 	if (so.on) {
-		for (int o = 32; o > 0; o >>= 1)
+		for (int o = 32; o > 0; o >>= 1) {
 			sof |= __shfl_xor(sof, o);
+			const unsigned long long t = __shfl_xor(scm, o);
+			scm = t > scm ? t : scm;
+		}
 		if (lane == 0 && sof)
 			publish_or(so.flags, sof);
+		// a count that cannot open the gate even with the source type's
+		// largest magnitude, 2^(8 VW - 1), is not worth its atomic (int into
+		// lng never publishes)
+		if (lane == 0 && scm && (VW >= 16 || ((uhge) scm << (VW > 0 ? 8 * VW - 1 : 0)) > (uhge) so.max))
+			publish_max(so.cmax, scm);
 	}
 }
 
@@ -1154,6 +1267,7 @@ __global__ __launch_bounds__(256) void
 k_gedge_sum(const GEdge *e, BUN ne, oid gmin, BUN ngrp, SOut so)
 {
 	uint32_t f = 0;
+	unsigned long long cm = 0;
 	for (BUN j = (BUN) blockIdx.x * blockDim.x + threadIdx.x; j < ne; j += (BUN) gridDim.x * blockDim.x) {
 		const oid g = e[j].g;
 		if ((j > 0 && e[j - 1].g == g) || g < gmin || g - gmin >= ngrp)
@@ -1164,12 +1278,17 @@ k_gedge_sum(const GEdge *e, BUN ne, oid gmin, BUN ngrp, SOut so)
 			s += ((uhge) e[q].hi << 64) | e[q].lo;
 			c += e[q].c;
 		}
-		f |= sout_put(so, g - gmin, s, c);
+		f |= sout_put(so, g - gmin, s, c, cm);
 	}
-	for (int o = 32; o > 0; o >>= 1)
+	for (int o = 32; o > 0; o >>= 1) {
 		f |= __shfl_xor(f, o);
+		const unsigned long long t = __shfl_xor(cm, o);
+		cm = t > cm ? t : cm;
+	}
 	if (__lane_id() == 0 && f)
 		publish_or(so.flags, f);
+	if (__lane_id() == 0 && cm)
+		publish_max(so.cmax, cm);
 }
 
 __global__ void
@@ -1490,17 +1609,24 @@ or_flags(uint32_t *flags, uint32_t f)
 
 // BATgroupsum per group (gdk_aggr.c:429-705): nil without a value, and
 // without skip_nils when a nil came after the first value (one group: any
-// nil); flags bit 0: a group's sum -- itself a prefix -- beyond the type's
-// range (overflow), bit 1: a nil result
+// nil).  The accumulators hold each group's total modulo 2^128 over all its
+// values, so GFlags bit 0 is raised only by a non-nil group: all its values
+// were added, its total is its last running sum, and a total outside the
+// range is an overflow.  A total inside the range proves nothing -- an earlier
+// running sum may have left it, a nil group stopped adding before its end --
+// so the kernel also leaves the largest count and the magnitude class, from
+// which the host decides whether the ordered decision has to run.
+// Bit 1: a nil result.
 __global__ __launch_bounds__(256) void
-k_gsum_out(GAcc acc, BUN ng, bool empty, int bt, bool skip_nils, hge max, void *out, uint32_t *flags)
+k_gsum_out(GAcc acc, BUN ng, bool empty, int bt, bool skip_nils, hge max, void *out,
+	   const unsigned long long *maxabs, GFlags *gf)
 {
 	uint32_t f = 0;
+	unsigned long long cm = 0;
 	for (BUN k = (BUN) blockIdx.x * blockDim.x + threadIdx.x; k < ng; k += (BUN) gridDim.x * blockDim.x) {
 		const hge sv = acc_sum(acc, k);
-		const unsigned long long c = acc.cnt[k];
-		if (sv > max || sv < -max)
-			f |= 1;
+		const unsigned long long c = empty ? 0 : acc.cnt[k];
+		cm = c > cm ? c : cm;
 		bool nil;
 		if (empty || c == 0)
 			nil = true;
@@ -1511,9 +1637,16 @@ k_gsum_out(GAcc acc, BUN ng, bool empty, int bt, bool skip_nils, hge max, void *
 		else
 			nil = acc.lastnil[k] > acc.firstval[k] + 1;
 		put_res_d(out, bt, k, nil ? 0 : sv, nil);
-		f |= nil ? 2u : 0u;
+		f |= nil ? 2u : (sv > max || sv < -max) ? 1u : 0u;
 	}
-	or_flags(flags, f);
+	or_flags(&gf->flags, f);
+	cm = block_reduce(cm, [](unsigned long long x, unsigned long long y) { return x > y ? x : y; });
+	if (threadIdx.x == 0) {
+		if (cm)
+			publish_max(&gf->cmax, cm);
+		if (blockIdx.x == 0)
+			gf->maxabs = *maxabs;
+	}
 }
 
 __global__ __launch_bounds__(256) void
@@ -1649,6 +1782,18 @@ read_flags(const void *dev, uint32_t *out)
 	if (h == nullptr || !hip_ok(hipMemcpyAsync(h, dev, 4, hipMemcpyDeviceToHost, stream()), "memcpy") || !sync())
 		return false;
 	*out = h[0];
+	return true;
+}
+
+// the same for BATgroupsum's GFlags block
+bool
+read_gflags(const GFlags *dev, GFlags *out)
+{
+	GFlags *h = (GFlags *) pinned(sizeof(GFlags));
+	if (h == nullptr || !hip_ok(hipMemcpyAsync(h, dev, sizeof(GFlags), hipMemcpyDeviceToHost, stream()), "memcpy") ||
+	    !sync())
+		return false;
+	*out = *h;
 	return true;
 }
 
@@ -2034,7 +2179,9 @@ k_gsum_rows(const void *base, oid off, BUN n, SOut so)
 			if (i >= n)
 				break;
 			const bool nil = is_nil(x[u]);
-			f |= sout_put(so, i, nil ? 0 : (uhge) (hge) x[u], nil ? 0 : 1);
+			// one value per group: its only running sum is the value itself
+			unsigned long long one = 0;
+			f |= sout_put(so, i, nil ? 0 : (uhge) (hge) x[u], nil ? 0 : 1, one);
 		}
 	}
 	for (int o = 32; o > 0; o >>= 1)
@@ -2046,17 +2193,20 @@ k_gsum_rows(const void *base, oid off, BUN n, SOut so)
 // BATgroupsum over sorted group ids straight into bn (see SOut); false
 // when the case does not apply
 bool
-gsum_sorted_direct(const AggrInit &a, mgdk_bat *b, mgdk_bat *bn, int tp, bool skip_nils, uint32_t *flags, uint32_t *hf,
+gsum_sorted_direct(const AggrInit &a, mgdk_bat *b, mgdk_bat *bn, int tp, bool skip_nils, GFlags *gf, GFlags *hf,
 		   int *rc)
 {
-	static const bool on = getenv("MGDK_GSUM_DIRECT") ? atoi(getenv("MGDK_GSUM_DIRECT")) != 0 : true;
+	uint32_t *flags = &gf->flags;
+	// read on every call, so that one process can run both forms
+	const char *ev = getenv("MGDK_GSUM_DIRECT");
+	const bool on = ev ? atoi(ev) != 0 : true;
 	const BUN ng = a.ngrp;
 	if (!on || !a.gsorted || ng <= 8 || a.ci.n == 0 || !(skip_nils || b->tnonil))
 		return false;
 	*rc = -1;
 	hipStream_t st = stream();
 	if (one_row_groups(a)) {
-		SOut so1{bn->theap, basetype(tp), tmax(tp), flags, true};
+		SOut so1{bn->theap, basetype(tp), tmax(tp), flags, true, &gf->cmax};
 		const oid off1 = a.ci.seq - b->hseqbase;
 		const dim3 g1(grid_for(a.ci.n, 256 * 8, 8192)), b1(256);
 		switch (b->twidth) {
@@ -2066,7 +2216,7 @@ gsum_sorted_direct(const AggrInit &a, mgdk_bat *b, mgdk_bat *bn, int tp, bool sk
 		case 8: hipLaunchKernelGGL(k_gsum_rows<8>, g1, b1, 0, st, b->theap, off1, a.ci.n, so1); break;
 		default: hipLaunchKernelGGL(k_gsum_rows<16>, g1, b1, 0, st, b->theap, off1, a.ci.n, so1); break;
 		}
-		if (read_flags(flags, hf))
+		if (read_gflags(gf, hf))
 			*rc = 0;
 		return true;
 	}
@@ -2075,16 +2225,16 @@ gsum_sorted_direct(const AggrInit &a, mgdk_bat *b, mgdk_bat *bn, int tp, bool sk
 	static const int ud = getenv("MGDK_GS_DIRECT_U") ? atoi(getenv("MGDK_GS_DIRECT_U")) : GS_UA;
 	const int u = b->twidth >= 16 ? GS_UA : (ud == 8 || ud == 32) ? ud : GS_U;
 	const BUN rw = 64 * (BUN) u, nr = (a.ci.n + rw - 1) / rw;
-	DevBuf eb(nr * 2 * sizeof(GEdge) + 64), mx(64);
-	if (!eb.p || !mx.p || !hip_ok(hipMemsetAsync(mx.p, 0, 8, st), "memset"))
+	DevBuf eb(nr * 2 * sizeof(GEdge) + 64);
+	if (!eb.p)
 		return true;
 	const oid off = a.ci.seq - b->hseqbase;
 	const bool vec = ((uintptr_t) a.gids & 15) == 0 && (((uintptr_t) b->theap + (uintptr_t) off * b->twidth) & 15) == 0;
-	SOut so{bn->theap, basetype(tp), tmax(tp), flags, true};
+	SOut so{bn->theap, basetype(tp), tmax(tp), flags, true, &gf->cmax};
 	const dim3 gs(grid_for(nr, 4, 65535u * 16u)), blk(256);
 	GAcc acc{};
 	GEdge *e = eb.as<GEdge>();
-	unsigned long long *m = mx.as<unsigned long long>();
+	unsigned long long *m = &gf->maxabs;   // zeroed with the flags by the caller
 	// results of 8 bytes or more stored from the lanes that finish the
 	// groups measured faster than staged in LDS (2.80 vs 3.07 ms for 600M
 	// rows at 16 rows per lane): no LDS, full occupancy
@@ -2102,8 +2252,123 @@ gsum_sorted_direct(const AggrInit &a, mgdk_bat *b, mgdk_bat *bn, int tp, bool sk
 	hipLaunchKernelGGL(k_gedge_sum, dim3(grid_for(2 * nr, 1024, 4096)), blk, 0, st, e, 2 * nr, a.min, ng, so);
 	// the flags read waits for the stream: eb goes back to the shared cache
 	// only after the kernels are done
-	if (read_flags(flags, hf))
+	if (read_gflags(gf, hf))
 		*rc = 0;
+	return true;
+}
+
+// The ordered decision of BATgroupsum (AGGR_SUM, gdk_aggr.c:429-705: the
+// range is checked after every add, in candidate order), run only when the
+// host's gate says a group may overflow.  One workgroup per group whose row
+// count times the magnitude bound exceeds max; the others cannot overflow.
+// The rows that the reference adds are one stretch of the group's rows:
+//   skip_nils          every row, nils skipped;
+//   else, one group    the rows before the first nil (the sum goes nil and
+//                      the adding ends);
+//   else               from the group's first value (it resets the sum, so
+//                      nils before it are forgotten) to the first nil after
+//                      it (a nil group skips its adds).
+// Each lane folds a contiguous piece of the stretch into (sum, largest and
+// smallest running sum) in 192 bits, and the pieces are joined in order.
+// perm / start as group_rows leaves them (start NULL: one group, every row,
+// ids range-checked here).  flags bit 0: a running sum left [-max, max].
+__global__ __launch_bounds__(256) void
+k_gsum_ordered(const void *base, int w, oid off, const uint32_t *perm, const uint64_t *start, const oid *gids,
+	       oid gseq, oid gmin, BUN ngrp, BUN n, bool skip_nils, hge max, uhge bound, uint32_t *flags)
+{
+	__shared__ unsigned long long s_pos[2];
+	// 0: not a row of the group, 1: a value, 2: nil
+	auto row = [&](BUN j, hge &v) -> int {
+		const BUN i = perm ? perm[j] : j;
+		if (start == nullptr) {
+			const oid g = gids ? gids[i] : gseq + i;
+			if (g < gmin || g - gmin >= ngrp)
+				return 0;
+		}
+		bool isnil;
+		v = ldv(base, w, off + i, isnil);
+		return isnil ? 2 : 1;
+	};
+	auto lower = [](unsigned long long x, unsigned long long y) { return x < y ? x : y; };
+	for (BUN k = blockIdx.x; k < ngrp; k += gridDim.x) {
+		const BUN j0 = start ? start[k] : 0, j1 = start ? start[k + 1] : n;
+		if (j1 == j0 || bound <= (uhge) max / (uhge) (j1 - j0))
+			continue;                // uniform for the workgroup
+		BUN lo = j0, hi = j1;
+		if (!skip_nils) {
+			// the first value and the first nil (one group), then the first nil
+			// after the first value (several groups)
+			hge v;
+			unsigned long long fv = ~0ull, fn = ~0ull;
+			for (BUN j = j0 + threadIdx.x; j < j1 && (fv == ~0ull || fn == ~0ull); j += blockDim.x) {
+				const int r = row(j, v);
+				if (r == 1 && fv == ~0ull)
+					fv = j;
+				if (r == 2 && fn == ~0ull)
+					fn = j;
+			}
+			fv = block_reduce(fv, lower);
+			fn = block_reduce(fn, lower);
+			if (threadIdx.x == 0) {
+				s_pos[0] = fv;
+				s_pos[1] = fn;
+			}
+			__syncthreads();
+			fv = s_pos[0];
+			fn = s_pos[1];
+			__syncthreads();
+			if (fv == ~0ull)
+				continue;            // no value: nothing is added
+			if (ngrp == 1) {
+				hi = fn < j1 ? fn : j1;
+			} else {
+				lo = fv;
+				fn = ~0ull;
+				for (BUN j = fv + 1 + threadIdx.x; j < j1 && fn == ~0ull; j += blockDim.x)
+					if (row(j, v) == 2)
+						fn = j;
+				fn = block_reduce(fn, lower);
+				if (threadIdx.x == 0)
+					s_pos[1] = fn;
+				__syncthreads();
+				fn = s_pos[1];
+				__syncthreads();
+				hi = fn < j1 ? fn : j1;
+			}
+		}
+		const BUN len = hi > lo ? hi - lo : 0, chunk = (len + 255) / 256;
+		const BUN a = threadIdx.x * chunk < len ? lo + threadIdx.x * chunk : hi;
+		const BUN e = a + chunk < hi ? a + chunk : hi;
+		Pfx p{};
+		for (BUN j = a; j < e; j++) {
+			hge v;
+			if (row(j, v) == 1)
+				pfx_add(p, v);
+		}
+		if (pfx_block_over(p, max))      // true in thread 0 only
+			publish_or(flags, 1u);
+	}
+}
+
+// runs k_gsum_ordered over a's groups; *over: a running sum left the range
+bool
+gsum_ordered(const AggrInit &a, mgdk_bat *b, int tp, bool skip_nils, unsigned long long maxabs, uint32_t *flags,
+	     bool *over)
+{
+	GroupRows gr(a.ci.n, a.ngrp);
+	if (!gr.ok() || group_rows(a, gr) < 0)
+		return false;
+	hipStream_t st = stream();
+	if (!hip_ok(hipMemsetAsync(flags, 0, 4, st), "memset"))
+		return false;
+	const BUN ng = a.ngrp;
+	hipLaunchKernelGGL(k_gsum_ordered, dim3((unsigned) (ng < 65535 ? ng : 65535)), dim3(256), 0, st, b->theap,
+			   b->twidth, a.ci.seq - b->hseqbase, gr.perm, gr.start_p, a.gids, a.gseq, a.min, ng, a.ci.n,
+			   skip_nils, tmax(tp), mag_bound_u(maxabs), flags);
+	uint32_t hf = 0;
+	if (!read_flags(flags, &hf))
+		return false;
+	*over = (hf & 1) != 0;
 	return true;
 }
 
@@ -2247,16 +2512,17 @@ mgdk_BATgroupsum(mgdk_bat *b, mgdk_bat *g, mgdk_bat *e, mgdk_bat *s, int tp, boo
 		return nullptr;
 	const BUN ng = a.ngrp;
 	mgdk_bat *bn = newbat(ng ? a.min : 0, tp, ng);
-	DevBuf fl(16);
-	if (bn == nullptr || fl.p == nullptr || !hip_ok(hipMemsetAsync(fl.p, 0, 16, stream()), "memset")) {
+	DevBuf fl(sizeof(GFlags));
+	if (bn == nullptr || fl.p == nullptr || !hip_ok(hipMemsetAsync(fl.p, 0, sizeof(GFlags), stream()), "memset")) {
 		mgdk_BBPunfix(bn);
 		return nullptr;
 	}
-	uint32_t hf = 0;
+	GFlags gf{};
+	uint32_t &hf = gf.flags;
 	if (ng) {
 		int rc = 0;
 		bool read = false;
-		if (gsum_sorted_direct(a, b, bn, tp, skip_nils, fl.as<uint32_t>(), &hf, &rc)) {
+		if (gsum_sorted_direct(a, b, bn, tp, skip_nils, fl.as<GFlags>(), &gf, &rc)) {
 			if (rc < 0) {
 				mgdk_BBPunfix(bn);
 				return nullptr;
@@ -2270,15 +2536,25 @@ mgdk_BATgroupsum(mgdk_bat *b, mgdk_bat *g, mgdk_bat *e, mgdk_bat *s, int tp, boo
 				return nullptr;
 			}
 			hipLaunchKernelGGL(k_gsum_out, dim3(grid_for(ng, 1024, 8192)), dim3(256), 0, stream(), acc, ng,
-					   a.ci.n == 0, basetype(tp), skip_nils, tmax(tp), bn->theap, fl.as<uint32_t>());
+					   a.ci.n == 0, basetype(tp), skip_nils, tmax(tp), bn->theap, mx, fl.as<GFlags>());
 		}
-		if (!read && !read_flags(fl.p, &hf)) {
+		if (!read && !read_gflags(fl.as<GFlags>(), &gf)) {
 			mgdk_BBPunfix(bn);
 			return nullptr;
 		}
-		if (hf & 1) {
-			// a prefix of a group could exceed the range only if its final sum
-			// does (the final sum is the last prefix)
+		// bit 0: a non-nil group's total, its last running sum, is beyond the
+		// range.  A total within the range decides nothing: an earlier running
+		// sum of the group may have left the range (the reference checks after
+		// every add), a total may have wrapped modulo 2^128, and a group that
+		// went nil stopped adding.  That needs count * bound > max in some
+		// group; only then the ordered decision runs, and it is exact.
+		bool over = (hf & 1) != 0;
+		if (!over && sum_may_overflow(gf.cmax, gf.maxabs, tmax(tp)) &&
+		    !gsum_ordered(a, b, tp, skip_nils, gf.maxabs, &fl.as<GFlags>()->flags, &over)) {
+			mgdk_BBPunfix(bn);
+			return nullptr;
+		}
+		if (over) {
 			seterr("22003!overflow in sum aggregate.\n");
 			mgdk_BBPunfix(bn);
 			return nullptr;

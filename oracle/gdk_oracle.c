@@ -1295,6 +1295,30 @@ ora_fsum(double *out, bool *isnil, const ora_bat *b, const ora_ci *ci, bool skip
 	return rc;
 }
 
+/* the atom names in the "type combination (sum(..)->..)" message */
+const char *ora_sum_tname(int t);
+const char *
+ora_sum_tname(int t)
+{
+	switch (t) {
+	case ORA_void: return "void";
+	case ORA_bit: return "bit";
+	case ORA_bte: return "bte";
+	case ORA_sht: return "sht";
+	case ORA_int: return "int";
+	case ORA_oid: return "oid";
+	case ORA_flt: return "flt";
+	case ORA_dbl: return "dbl";
+	case ORA_lng: return "lng";
+	case ORA_hge: return "hge";
+	case ORA_date: return "date";
+	case ORA_daytime: return "daytime";
+	case ORA_timestamp: return "timestamp";
+	case ORA_str: return "str";
+	}
+	return "any";
+}
+
 int
 ora_sum(void *res, int tp, const ora_bat *b, const ora_bat *s,
 	bool skip_nils, bool nil_if_empty)
@@ -1338,8 +1362,10 @@ ora_sum(void *res, int tp, const ora_bat *b, const ora_bat *s,
 		*(double *) res = isnil ? nan("") : avg * (double) cnt;
 		return 0;
 	}
-	if (tp != ORA_lng && tp != ORA_hge && tp != ORA_int) {
-		ora_seterr("sum: unsupported result type");
+	/* every integer result, narrower ones included (their sums overflow
+	 * sooner); dosum's "unsupported" exit for the rest */
+	if (type_max(tp) == 0 || type_max(t) == 0) {
+		ora_seterr("type combination (sum(%s)->%s) not supported.\n", ora_sum_tname(b->type), ora_sum_tname(tp));
 		return -1;
 	}
 	ora_hge max = type_max(tp), acc = 0;
@@ -1355,7 +1381,7 @@ ora_sum(void *res, int tp, const ora_bat *b, const ora_bat *s,
 		}
 		ora_hge z;
 		if (__builtin_add_overflow(acc, v, &z) || z < -max || z > max) {
-			ora_seterr("22003!overflow in sum aggregate.");
+			ora_seterr("22003!overflow in sum aggregate.\n");
 			return -1;
 		}
 		acc = z;

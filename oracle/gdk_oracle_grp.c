@@ -458,6 +458,19 @@ ora_groupsum(const ora_bat *b, const ora_bat *g, const ora_bat *e,
 		}
 		return bn;
 	}
+	{
+		/* integers into integers, narrower results included; dosum's
+		 * "unsupported" exit for the rest */
+		const char *ora_sum_tname(int t);
+		const int bt = b->type;
+		const bool bint = bt == ORA_bit || bt == ORA_bte || bt == ORA_sht || bt == ORA_int || bt == ORA_date ||
+			bt == ORA_lng || bt == ORA_hge;
+		const bool rint = tp == ORA_bte || tp == ORA_sht || tp == ORA_int || tp == ORA_lng || tp == ORA_hge;
+		if (!bint || !rint) {
+			ora_seterr("type combination (sum(%s)->%s) not supported.\n", ora_sum_tname(bt), ora_sum_tname(tp));
+			return NULL;
+		}
+	}
 	ora_bat *bn = ora_new(tp, a.ngrp, a.ngrp ? a.min : 0);
 	ora_hge *acc = calloc(a.ngrp + 1, sizeof(ora_hge));
 	uint8_t *st = calloc(a.ngrp + 1, 1);    /* 0 unseen, 1 value, 2 nil */
@@ -474,9 +487,10 @@ ora_groupsum(const ora_bat *b, const ora_bat *g, const ora_bat *e,
 	 * any nil makes the sum nil (:440-470). */
 	for (uint64_t i = 0; i < a.ci.n; i++) {
 		ora_oid gid;
-		if (a.ngrp == 1)
-			gid = 0;
-		else if (!aggr_gid(&a, i, &gid))
+		/* one group: the reference's single-group loops (:440-470) read no
+		 * ids; a row whose id is nil or outside e is skipped here as in the
+		 * loop with groups, the rule every grouped aggregate follows */
+		if (!aggr_gid(&a, i, &gid))
 			continue;
 		ora_hge v;
 		if (val_at(b, ci_get(&a.ci, i) - b->hseqbase, &v)) {
