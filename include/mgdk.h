@@ -85,6 +85,21 @@ int mgdk_init(int device);                       /* select HIP device */
  * (mgdk_GDKanalyticalprod, float BATgroupprod) are always replayed.
  * Process-wide; returns the previous value. */
 mgdk_BUN mgdk_set_fp_parallel_min(mgdk_BUN rows);
+
+/* Column images: an int / date / lng column whose non-nil values span at
+ * most 254 (65534) keeps, once a reader has asked for it, a copy of 1 (2)
+ * bytes per row -- value minus the column's minimum, all ones for nil --
+ * that the fused Q6 reads in place of the 8-byte discount and quantity.  It
+ * is an accelerator like a hash or an order index: invisible here, built on
+ * first use, dropped by any write to the tail.  Images are built only for
+ * columns of at least `rows` rows (default 2^20, or the environment's
+ * MGDK_COLIMG_MIN read at load; MGDK_BUN_NONE: never).  Process-wide; returns
+ * the previous value.  Tuning hook, not ABI. */
+mgdk_BUN mgdk_set_colimg_min(mgdk_BUN rows);
+/* state of b's column image: 0 unknown (none built, or the tail or count
+ * changed since), -1 ineligible, 1 ready (then *width = 1 | 2 and *base = the
+ * value of code 0; either may be NULL).  Never builds.  Tests. */
+int mgdk_colimg_info(const mgdk_bat *b, int *width, int64_t *base);
 const char *mgdk_GDKerrbuf(void);                /* gdk.h:1947 GDKerrbuf */
 void mgdk_GDKclrerr(void);
 int mgdk_sync(void);                             /* drain calling thread's stream */

@@ -80,6 +80,23 @@ struct Priv {
 	// so an index the parent gets later is seen; a written tail leaves both
 	struct OidxSlot *oidx, *poidx;
 	bool view;               // a BATslice view: BATsort builds no index for it
+	// the column image (see ColImg): a frame-of-reference copy of an int /
+	// date / lng tail in 1 or 2 bytes per row, built on first use by a reader
+	// that asks for it (colimg_get) and dropped with img8 whenever the tail
+	// is written.  cimg_state: 0 unknown, -1 ineligible (remembered, so a
+	// wide column is scanned once), 1 ready; cimg_n / cimg_tail are the
+	// count and tail pointer the state was decided for
+	Heap *cimg;
+	int cimg_state, cimg_w;
+	int64_t cimg_base;
+	BUN cimg_n;
+	const void *cimg_tail;
+};
+// a column image: code = value - base in `width` bytes, all ones = nil
+struct ColImg {
+	const void *codes;
+	int width;               // 1 | 2
+	int64_t base;            // the column's smallest non-nil value
 };
 struct OidxSlot {
 	int refs;
@@ -105,7 +122,12 @@ int width_of(int tt);
 // the 1-byte image of b's oid tail, or NULL (see Priv::img8)
 const uint8_t *img8_get(const mgdk_bat *b);
 uint8_t *img8_new(mgdk_bat *b);     // allocate an image for b->count values
-void img8_drop(mgdk_bat *b);        // drops every accelerator of the tail (img8, smap)
+void img8_drop(mgdk_bat *b);        // drops every accelerator of the tail (img8, smap, column image)
+// b's column image, built first (on the caller's stream, under a lock) when
+// b has none yet and the policy (mgdk_set_colimg_min) allows one; false when
+// b is ineligible, a view, too small, or the image cannot be allocated: the
+// caller then reads the tail itself
+bool colimg_get(mgdk_bat *b, ColImg *im);
 bool smap_get(const mgdk_bat *b, SelMap *m);
 void smap_set(mgdk_bat *b, Heap *h, const SelMap &m);   // takes a reference on h
 // b's order index (a reference on its heap, release with heap_decref; the

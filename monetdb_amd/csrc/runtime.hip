@@ -525,11 +525,26 @@ img8_new(mgdk_bat *b)
 }
 
 static void oidx_leave(Priv *p);
+// guards every Priv's column image fields (build, publish, drop, free)
+static std::mutex cimg_mu;
+
+static void
+cimg_reset(Priv *p)
+{
+	std::lock_guard<std::mutex> g(cimg_mu);
+	heap_decref(p->cimg);
+	p->cimg = nullptr;
+	p->cimg_state = 0;
+	p->cimg_n = 0;
+	p->cimg_tail = nullptr;
+}
 
 void
 img8_drop(mgdk_bat *b)
 {
 	Priv *p = (Priv *) b->priv;
+	if (p)
+		cimg_reset(p);
 	if (p && p->img8) {
 		heap_decref(p->img8);
 		p->img8 = nullptr;
@@ -1228,6 +1243,7 @@ mgdk_BBPunfix(mgdk_bat *b)
 		heap_decref(p->tvheap);
 		heap_decref(p->img8);
 		heap_decref(p->smap);
+		heap_decref(p->cimg);
 		oidx_leave(p);
 		delete p;
 	}
@@ -1590,4 +1606,214 @@ extern "C" mgdk_BUN
 mgdk_set_fp_parallel_min(mgdk_BUN rows)
 {
 	return (mgdk_BUN) g_fp_par_min.exchange((uint64_t) rows);
+}
+
+// ---- column images (Priv::cimg) ---------------------------------------------
+static uint64_t
+colimg_min_env()
+{
+	const char *e = getenv("MGDK_COLIMG_MIN");
+	return e && *e ? (uint64_t) strtoull(e, nullptr, 0) : (uint64_t) 1 << 20;
+}
+static std::atomic<uint64_t> g_colimg_min{colimg_min_env()};
+
+// cell[0] / cell[1]: smallest / largest non-nil value (start at INT64_MAX /
+// INT64_MIN: a column of nils leaves cell[0] > cell[1])
+template <typename T>
+__global__ __launch_bounds__(256) void
+k_cimg_minmax(const T *v, BUN n, long long *cell)
+{
+	const T nil = (T) ((T) 1 << (8 * sizeof(T) - 1));
+	long long lo = INT64_MAX, hi = INT64_MIN;
+	for (BUN i = (BUN) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (BUN) gridDim.x * blockDim.x) {
+		const T x = v[i];
+		if (x != nil) {
+			lo = x < lo ? x : lo;
+			hi = x > hi ? x : hi;
+		}
+	}
+	for (int o = 32; o > 0; o >>= 1) {
+		const long long l2 = __shfl_xor(lo, o), h2 = __shfl_xor(hi, o);
+		lo = l2 < lo ? l2 : lo;
+		hi = h2 > hi ? h2 : hi;
+	}
+	if (__lane_id() == 0 && lo <= hi) {
+		atomicMin(cell, lo);
+		atomicMax(cell + 1, hi);
+	}
+}
+
+// out[i] = v[i] - base, all ones for nil; cell[2] is set when a non-nil value
+// lies outside [base, base + span] (extremes taken from tminpos / tmaxpos that
+// did not hold): the image is then thrown away
+template <typename T, typename C>
+__global__ __launch_bounds__(256) void
+k_cimg_encode(const T *v, BUN n, long long base, unsigned long long span, C *out, long long *cell)
+{
+	const T nil = (T) ((T) 1 << (8 * sizeof(T) - 1));
+	bool bad = false;
+	for (BUN i = (BUN) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (BUN) gridDim.x * blockDim.x) {
+		const T x = v[i];
+		C c = (C) ~(C) 0;
+		if (x != nil) {
+			// unsigned difference: exact for any pair, huge when x < base
+			const unsigned long long d = (unsigned long long) (long long) x - (unsigned long long) base;
+			if (d > span)
+				bad = true;
+			else
+				c = (C) d;
+		}
+		out[i] = c;
+	}
+	if (bad)
+		cell[2] = 1;
+}
+
+template <typename T>
+static void
+cimg_encode(const void *tail, BUN n, int64_t base, uint64_t span, int w, void *out, long long *cell, hipStream_t st)
+{
+	const dim3 g(grid_for(n, 1024, 256 * 16)), blk(256);
+	if (w == 1)
+		hipLaunchKernelGGL((k_cimg_encode<T, uint8_t>), g, blk, 0, st, (const T *) tail, n, (long long) base,
+				   (unsigned long long) span, (uint8_t *) out, cell);
+	else
+		hipLaunchKernelGGL((k_cimg_encode<T, uint16_t>), g, blk, 0, st, (const T *) tail, n, (long long) base,
+				   (unsigned long long) span, (uint16_t *) out, cell);
+}
+
+namespace mgdk {
+bool
+colimg_get(mgdk_bat *b, ColImg *im)
+{
+	Priv *p = (Priv *) b->priv;
+	if (p == nullptr || p->view || b->theap == nullptr ||
+	    (b->ttype != MGDK_int && b->ttype != MGDK_date && b->ttype != MGDK_lng))
+		return false;
+	const BUN n = b->count;
+	// one lock for look-up, build and publication: a second caller waits for
+	// the builder and then finds the image (or the ineligible mark)
+	std::lock_guard<std::mutex> g(cimg_mu);
+	if (p->cimg_state != 0 && (p->cimg_n != n || p->cimg_tail != b->theap)) {
+		// the descriptor was edited since: what is kept describes other rows
+		heap_decref(p->cimg);
+		p->cimg = nullptr;
+		p->cimg_state = 0;
+	}
+	if (p->cimg_state == 1) {
+		im->codes = p->cimg->base;
+		im->width = p->cimg_w;
+		im->base = p->cimg_base;
+		return true;
+	}
+	const uint64_t thr = g_colimg_min.load(std::memory_order_relaxed);
+	if (p->cimg_state < 0 || thr == (uint64_t) MGDK_BUN_NONE || n == 0 || n < thr)
+		return false;
+
+	hipStream_t st = stream();
+	void *mb = meta_buf();
+	long long *h = (long long *) pinned(64);
+	if (mb == nullptr || h == nullptr)
+		return false;
+	long long *cell = (long long *) ((char *) mb + 2048);
+	const bool wide = b->twidth == 8;
+	const size_t w = wide ? 8 : 4;
+	auto ineligible = [&]() {
+		p->cimg_state = -1;
+		p->cimg_n = n;
+		p->cimg_tail = b->theap;
+		return false;
+	};
+	int64_t lo = 0, hi = -1;
+	bool known = false;
+	if (b->tnonil && b->tminpos < n && b->tmaxpos < n) {
+		// the extremes are known: no min/max pass (the encode verifies them)
+		if (!hip_ok(hipMemcpyAsync(h, (const char *) b->theap + b->tminpos * w, w, hipMemcpyDeviceToHost, st), "memcpy") ||
+		    !hip_ok(hipMemcpyAsync(h + 1, (const char *) b->theap + b->tmaxpos * w, w, hipMemcpyDeviceToHost, st), "memcpy") ||
+		    !sync_data())
+			return false;
+		int32_t l4, h4;
+		memcpy(&l4, h, 4);
+		memcpy(&h4, h + 1, 4);
+		lo = wide ? h[0] : l4;
+		hi = wide ? h[1] : h4;
+		known = lo <= hi && (wide ? lo != INT64_MIN : l4 != INT32_MIN);
+	}
+	for (int pass = known ? 0 : 1; pass < 2; pass++) {
+		if (pass == 1) {
+			h[0] = INT64_MAX;
+			h[1] = INT64_MIN;
+			if (!hip_ok(hipMemcpyAsync(cell, h, 16, hipMemcpyHostToDevice, st), "memcpy"))
+				return false;
+			const dim3 grid(grid_for(n, 1024, 256 * 16)), blk(256);
+			if (wide)
+				hipLaunchKernelGGL((k_cimg_minmax<int64_t>), grid, blk, 0, st, (const int64_t *) b->theap, n, cell);
+			else
+				hipLaunchKernelGGL((k_cimg_minmax<int32_t>), grid, blk, 0, st, (const int32_t *) b->theap, n, cell);
+			if (!hip_ok(hipMemcpyAsync(h, cell, 16, hipMemcpyDeviceToHost, st), "memcpy") || !sync_data())
+				return false;
+			lo = h[0];
+			hi = h[1];
+			if (lo > hi)
+				return ineligible();   // no non-nil value
+		}
+		// max - min as an unsigned difference: exact over the whole lng range
+		const uint64_t span = (uint64_t) hi - (uint64_t) lo;
+		if (span > 65534)
+			return ineligible();
+		const int cw = span <= 254 ? 1 : 2;
+		Heap *img = heap_new((size_t) n * cw);
+		if (img == nullptr)
+			return false;              // stays unknown: the caller reads the tail
+		bool ok = hip_ok(hipMemsetAsync(cell + 2, 0, 8, st), "memset");
+		if (ok) {
+			if (wide)
+				cimg_encode<int64_t>(b->theap, n, lo, span, cw, img->base, cell, st);
+			else
+				cimg_encode<int32_t>(b->theap, n, lo, span, cw, img->base, cell, st);
+			ok = hip_ok(hipMemcpyAsync(h + 2, cell + 2, 8, hipMemcpyDeviceToHost, st), "memcpy") && sync_data();
+		}
+		if (ok && h[2] == 0) {
+			p->cimg = img;
+			p->cimg_w = cw;
+			p->cimg_base = lo;
+			p->cimg_n = n;
+			p->cimg_tail = b->theap;
+			p->cimg_state = 1;
+			im->codes = img->base;
+			im->width = cw;
+			im->base = lo;
+			return true;
+		}
+		heap_decref(img);
+		if (!ok)
+			return false;
+		// the positions kept with the column did not hold its extremes: scan
+	}
+	return false;
+}
+}  // namespace mgdk
+
+extern "C" mgdk_BUN
+mgdk_set_colimg_min(mgdk_BUN rows)
+{
+	return (mgdk_BUN) g_colimg_min.exchange((uint64_t) rows);
+}
+
+extern "C" int
+mgdk_colimg_info(const mgdk_bat *b, int *width, int64_t *base)
+{
+	const Priv *p = b ? (const Priv *) b->priv : nullptr;
+	if (p == nullptr)
+		return 0;
+	std::lock_guard<std::mutex> g(cimg_mu);
+	if (p->cimg_state == 0 || p->cimg_n != b->count || p->cimg_tail != b->theap)
+		return 0;
+	if (p->cimg_state == 1) {
+		if (width)
+			*width = p->cimg_w;
+		if (base)
+			*base = p->cimg_base;
+	}
+	return p->cimg_state;
 }

@@ -30,6 +30,7 @@
 #include <atomic>
 
 #include "mgdk_internal.h"
+#include "q6codes.h"
 
 using namespace mgdk;
 
@@ -148,6 +149,12 @@ struct Q6Args {
 	int64_t dlo, dhi, qmax;
 	unsigned long long *out;   // [2] 128-bit revenue
 	struct Q6Part *parts;      // k_q6c / k_q6s: one partial per workgroup (NULL: atomics into out)
+	// the image variants of k_q6s: column images of discount / quantity (NULL:
+	// the raw column) and the predicates as code bounds (q6codes.h)
+	const void *dimg, *qimg;
+	int64_t dbase;             // discount = dbase + code
+	uint32_t dclo, dchi, qk;   // dclo <= discount code <= dchi, quantity code < qk
+	int dw, qw;                // image widths (host side: picks the instantiation)
 };
 
 // one workgroup's exact revenue and (k_q6s) line count: written once per
@@ -381,11 +388,191 @@ q6_ld(const int64_t *col, uint64_t chunk, uint64_t r, unsigned boff, bool live, 
 	}
 }
 
-template <int UNROLL, bool BUF = false>
+// Column images (Priv::cimg, runtime.hip) in the cascade: discount and / or
+// quantity are read as 1- or 2-byte codes (DW / QW = the image's width, 0 =
+// the raw lng column as above) with the same row-to-lane mapping, so a lane
+// loads the codes of its row pair with one 2- or 4-byte buffer load and a
+// dead lane's out-of-range offset again costs no memory access.  A dead
+// lane's zeros are a VALID code: its rows stay out through m[][] alone.  The
+// predicates are compared in the code domain (q6_code_bounds: the nil code,
+// all ones, lies above every bound), the product takes base + code, which is
+// the stored value.
+template <int W>
+__device__ __forceinline__ uint32_t
+q6_ldimg(const void *img, uint64_t chunk, unsigned half, unsigned lane, bool live)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__) && !defined(__gfx942__)
+#error "q6_ldimg: buffer descriptor word 3 is laid out for gfx942 / gfx950 only"
+#endif
+	__amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *) ((const char *) img + chunk * (256 * W)),
+								      (short) 0, 256 * W, 0x00020000);
+	const unsigned off = live ? (128u * half + 2u * lane) * W : 0x80000000u;
+	if constexpr (W == 1)
+		return (uint32_t) (unsigned short) __builtin_amdgcn_raw_buffer_load_b16(rs, off, 0, 0);
+	else
+		return (uint32_t) __builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0);
+}
+
+// 128-B lines one half-chunk load (128 rows, lane l at rows 2l, 2l+1) touches,
+// from the ballot of its live lanes: W = 0 the raw lng column (8 lanes per
+// line), 1 / 2 an image of that width (64 / 32 lanes per line; the image
+// heap and so every half chunk starts on a line)
+template <int W>
+__device__ __forceinline__ uint32_t
+q6_ldlines(uint64_t b)
+{
+	if constexpr (W == 1)
+		return b != 0;
+	else if constexpr (W == 2)
+		return ((uint32_t) b != 0) + ((uint32_t) (b >> 32) != 0);
+	else {
+		b |= b >> 1;
+		b |= b >> 2;
+		b |= b >> 4;
+		return (uint32_t) __popcll(b & 0x0101010101010101ull);
+	}
+}
+
+// the cascade over U chunks (c, c + nw, ...) of 256 rows, all loads of one
+// column in flight together
+template <int U, bool BUF, int DW, int QW>
+__device__ __forceinline__ void
+q6s_chunks(const Q6Args &a, uint64_t c, uint64_t nw, unsigned lane, const void *z, hge &acc, uint32_t &nlines)
+{
+	typedef int32_t i2 __attribute__((ext_vector_type(2)));
+	typedef int64_t l2 __attribute__((ext_vector_type(2)));
+	i2 s0[U], s1[U];
+	l2 v0[U], v1[U], d0[U], d1[U];
+	uint32_t dc0[U], dc1[U], qc0[U], qc1[U];
+	bool m[U][4];
+#pragma unroll
+	for (int u = 0; u < U; u++) {
+		const uint64_t r0 = (c + u * nw) * 256 + 2 * lane, r1 = r0 + 128;
+		s0[u] = __builtin_nontemporal_load((const i2 *) (a.sd + r0));
+		s1[u] = __builtin_nontemporal_load((const i2 *) (a.sd + r1));
+	}
+#pragma unroll
+	for (int u = 0; u < U; u++) {
+		const int32_t sd[4] = {s0[u][0], s0[u][1], s1[u][0], s1[u][1]};
+#pragma unroll
+		for (int k = 0; k < 4; k++)
+			m[u][k] = sd[k] != INT32_MIN && sd[k] >= a.d0 && sd[k] < a.d1;
+	}
+	// discount where the date holds
+#pragma unroll
+	for (int u = 0; u < U; u++) {
+		const uint64_t r0 = (c + u * nw) * 256 + 2 * lane, r1 = r0 + 128;
+		const bool a0 = m[u][0] || m[u][1], a1 = m[u][2] || m[u][3];
+		nlines += q6_ldlines<DW>(__ballot(a0)) + q6_ldlines<DW>(__ballot(a1));
+		if constexpr (DW != 0) {
+			dc0[u] = q6_ldimg<DW>(a.dimg, c + u * nw, 0, lane, a0);
+			dc1[u] = q6_ldimg<DW>(a.dimg, c + u * nw, 1, lane, a1);
+		} else {
+			long long t0[2], t1[2];
+			q6_ld<BUF>(a.disc, c + u * nw, r0, 16u * lane, a0, z, t0);
+			q6_ld<BUF>(a.disc, c + u * nw, r1, 1024u + 16u * lane, a1, z, t1);
+			d0[u].x = t0[0];
+			d0[u].y = t0[1];
+			d1[u].x = t1[0];
+			d1[u].y = t1[1];
+		}
+	}
+#pragma unroll
+	for (int u = 0; u < U; u++) {
+		if constexpr (DW != 0) {
+			const uint32_t cm = (1u << (8 * DW)) - 1;
+			const uint32_t dc[4] = {dc0[u] & cm, dc0[u] >> (8 * DW), dc1[u] & cm, dc1[u] >> (8 * DW)};
+#pragma unroll
+			for (int k = 0; k < 4; k++)
+				m[u][k] = m[u][k] && dc[k] >= a.dclo && dc[k] <= a.dchi;
+		} else {
+			const int64_t di[4] = {d0[u][0], d0[u][1], d1[u][0], d1[u][1]};
+#pragma unroll
+			for (int k = 0; k < 4; k++)
+				m[u][k] = m[u][k] && di[k] != INT64_MIN && di[k] >= a.dlo && di[k] <= a.dhi;
+		}
+	}
+	// quantity where date and discount hold
+#pragma unroll
+	for (int u = 0; u < U; u++) {
+		const uint64_t r0 = (c + u * nw) * 256 + 2 * lane, r1 = r0 + 128;
+		const bool a0 = m[u][0] || m[u][1], a1 = m[u][2] || m[u][3];
+		nlines += q6_ldlines<QW>(__ballot(a0)) + q6_ldlines<QW>(__ballot(a1));
+		if constexpr (QW != 0) {
+			qc0[u] = q6_ldimg<QW>(a.qimg, c + u * nw, 0, lane, a0);
+			qc1[u] = q6_ldimg<QW>(a.qimg, c + u * nw, 1, lane, a1);
+		} else {
+			long long t0[2], t1[2];
+			q6_ld<BUF>(a.qty, c + u * nw, r0, 16u * lane, a0, z, t0);
+			q6_ld<BUF>(a.qty, c + u * nw, r1, 1024u + 16u * lane, a1, z, t1);
+			v0[u].x = t0[0];
+			v0[u].y = t0[1];
+			v1[u].x = t1[0];
+			v1[u].y = t1[1];
+		}
+	}
+#pragma unroll
+	for (int u = 0; u < U; u++) {
+		if constexpr (QW != 0) {
+			const uint32_t cm = (1u << (8 * QW)) - 1;
+			const uint32_t qc[4] = {qc0[u] & cm, qc0[u] >> (8 * QW), qc1[u] & cm, qc1[u] >> (8 * QW)};
+#pragma unroll
+			for (int k = 0; k < 4; k++)
+				m[u][k] = m[u][k] && qc[k] < a.qk;
+		} else {
+			const int64_t q[4] = {v0[u][0], v0[u][1], v1[u][0], v1[u][1]};
+#pragma unroll
+			for (int k = 0; k < 4; k++)
+				m[u][k] = m[u][k] && q[k] != INT64_MIN && q[k] < a.qmax;
+		}
+	}
+	// extendedprice where all three hold
+#pragma unroll
+	for (int u = 0; u < U; u++) {
+		const uint64_t r0 = (c + u * nw) * 256 + 2 * lane, r1 = r0 + 128;
+		const bool a0 = m[u][0] || m[u][1], a1 = m[u][2] || m[u][3];
+		nlines += q6_ldlines<0>(__ballot(a0)) + q6_ldlines<0>(__ballot(a1));
+		{
+			long long t0[2], t1[2];
+			q6_ld<BUF>(a.price, c + u * nw, r0, 16u * lane, a0, z, t0);
+			q6_ld<BUF>(a.price, c + u * nw, r1, 1024u + 16u * lane, a1, z, t1);
+			v0[u].x = t0[0];
+			v0[u].y = t0[1];
+			v1[u].x = t1[0];
+			v1[u].y = t1[1];
+		}
+	}
+#pragma unroll
+	for (int u = 0; u < U; u++) {
+		const int64_t p[4] = {v0[u][0], v0[u][1], v1[u][0], v1[u][1]};
+		int64_t di[4];
+		if constexpr (DW != 0) {
+			const uint32_t cm = (1u << (8 * DW)) - 1;
+			di[0] = a.dbase + (int64_t) (dc0[u] & cm);
+			di[1] = a.dbase + (int64_t) (dc0[u] >> (8 * DW));
+			di[2] = a.dbase + (int64_t) (dc1[u] & cm);
+			di[3] = a.dbase + (int64_t) (dc1[u] >> (8 * DW));
+		} else {
+			di[0] = d0[u][0];
+			di[1] = d0[u][1];
+			di[2] = d1[u][0];
+			di[3] = d1[u][1];
+		}
+#pragma unroll
+		for (int k = 0; k < 4; k++)
+			if (m[u][k] && p[k] != INT64_MIN)
+				acc += (hge) p[k] * (hge) di[k];
+	}
+}
+
+// DW / QW != 0 (image variants): the chunks left over by the unrolled loop
+// run the cascade too, one at a time -- read in full they would be a
+// visible share of what the image variants read at all
+template <int UNROLL, bool BUF = false, int DW = 0, int QW = 0>
 __global__ __launch_bounds__(256) void
 k_q6s(Q6Args a, const int64_t *zline)
 {
-	typedef int32_t i2 __attribute__((ext_vector_type(2)));
+	static_assert(BUF || (DW == 0 && QW == 0), "column images are read with buffer loads");
 	typedef int64_t l2 __attribute__((ext_vector_type(2)));
 	hge acc = 0;
 	uint32_t nlines = 0;
@@ -393,110 +580,24 @@ k_q6s(Q6Args a, const int64_t *zline)
 	const uint64_t nch = a.n / 256;
 	const uint64_t nw = (uint64_t) gridDim.x * (blockDim.x / 64);
 	const l2 *z = (const l2 *) zline + ((((uint64_t) blockIdx.x * blockDim.x + threadIdx.x)) & (Q6_ZBYTES / 16 - 1));
-	// 128-B lines (8 lanes x 16 B) with at least one active lane in a ballot
-	auto lines = [](uint64_t b) -> uint32_t {
-		b |= b >> 1;
-		b |= b >> 2;
-		b |= b >> 4;
-		return (uint32_t) __popcll(b & 0x0101010101010101ull);
-	};
-	uint64_t c = ((uint64_t) blockIdx.x * blockDim.x + threadIdx.x) / 64;
-	for (; c + (UNROLL - 1) * nw < nch; c += UNROLL * nw) {
-		i2 s0[UNROLL], s1[UNROLL];
-		l2 v0[UNROLL], v1[UNROLL], d0[UNROLL], d1[UNROLL];
-		bool m[UNROLL][4];
-#pragma unroll
-		for (int u = 0; u < UNROLL; u++) {
-			const uint64_t r0 = (c + u * nw) * 256 + 2 * lane, r1 = r0 + 128;
-			s0[u] = __builtin_nontemporal_load((const i2 *) (a.sd + r0));
-			s1[u] = __builtin_nontemporal_load((const i2 *) (a.sd + r1));
-		}
-#pragma unroll
-		for (int u = 0; u < UNROLL; u++) {
-			const int32_t sd[4] = {s0[u][0], s0[u][1], s1[u][0], s1[u][1]};
-#pragma unroll
-			for (int k = 0; k < 4; k++)
-				m[u][k] = sd[k] != INT32_MIN && sd[k] >= a.d0 && sd[k] < a.d1;
-		}
-		// discount where the date holds
-#pragma unroll
-		for (int u = 0; u < UNROLL; u++) {
-			const uint64_t r0 = (c + u * nw) * 256 + 2 * lane, r1 = r0 + 128;
-			const bool a0 = m[u][0] || m[u][1], a1 = m[u][2] || m[u][3];
-			nlines += lines(__ballot(a0)) + lines(__ballot(a1));
-			{
-				long long t0[2], t1[2];
-				q6_ld<BUF>(a.disc, c + u * nw, r0, 16u * lane, a0, z, t0);
-				q6_ld<BUF>(a.disc, c + u * nw, r1, 1024u + 16u * lane, a1, z, t1);
-				d0[u].x = t0[0];
-				d0[u].y = t0[1];
-				d1[u].x = t1[0];
-				d1[u].y = t1[1];
+	// the wave's chunk index, told to the compiler as wave-uniform: the
+	// buffer descriptors built from it then live in scalar registers (taken
+	// for divergent, every buffer load was wrapped in a waterfall loop)
+	uint64_t c = (uint64_t) blockIdx.x * (blockDim.x / 64) + (unsigned) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
+	for (; c + (UNROLL - 1) * nw < nch; c += UNROLL * nw)
+		q6s_chunks<UNROLL, BUF, DW, QW>(a, c, nw, lane, z, acc, nlines);
+	if constexpr (DW != 0 || QW != 0) {
+		for (; c < nch; c += nw)
+			q6s_chunks<1, BUF, DW, QW>(a, c, nw, lane, z, acc, nlines);
+	} else {
+		for (; c < nch; c += nw) {
+			const uint64_t r0 = c * 256 + 2 * lane, r1 = r0 + 128;
+			for (int k = 0; k < 2; k++) {
+				acc += q6_row(a, a.sd[r0 + k], a.disc[r0 + k], a.qty[r0 + k], a.price[r0 + k]);
+				acc += q6_row(a, a.sd[r1 + k], a.disc[r1 + k], a.qty[r1 + k], a.price[r1 + k]);
 			}
+			nlines += 3 * 16;                        // counted as fully read
 		}
-#pragma unroll
-		for (int u = 0; u < UNROLL; u++) {
-			const int64_t di[4] = {d0[u][0], d0[u][1], d1[u][0], d1[u][1]};
-#pragma unroll
-			for (int k = 0; k < 4; k++)
-				m[u][k] = m[u][k] && di[k] != INT64_MIN && di[k] >= a.dlo && di[k] <= a.dhi;
-		}
-		// quantity where date and discount hold
-#pragma unroll
-		for (int u = 0; u < UNROLL; u++) {
-			const uint64_t r0 = (c + u * nw) * 256 + 2 * lane, r1 = r0 + 128;
-			const bool a0 = m[u][0] || m[u][1], a1 = m[u][2] || m[u][3];
-			nlines += lines(__ballot(a0)) + lines(__ballot(a1));
-			{
-				long long t0[2], t1[2];
-				q6_ld<BUF>(a.qty, c + u * nw, r0, 16u * lane, a0, z, t0);
-				q6_ld<BUF>(a.qty, c + u * nw, r1, 1024u + 16u * lane, a1, z, t1);
-				v0[u].x = t0[0];
-				v0[u].y = t0[1];
-				v1[u].x = t1[0];
-				v1[u].y = t1[1];
-			}
-		}
-#pragma unroll
-		for (int u = 0; u < UNROLL; u++) {
-			const int64_t q[4] = {v0[u][0], v0[u][1], v1[u][0], v1[u][1]};
-#pragma unroll
-			for (int k = 0; k < 4; k++)
-				m[u][k] = m[u][k] && q[k] != INT64_MIN && q[k] < a.qmax;
-		}
-		// extendedprice where all three hold
-#pragma unroll
-		for (int u = 0; u < UNROLL; u++) {
-			const uint64_t r0 = (c + u * nw) * 256 + 2 * lane, r1 = r0 + 128;
-			const bool a0 = m[u][0] || m[u][1], a1 = m[u][2] || m[u][3];
-			nlines += lines(__ballot(a0)) + lines(__ballot(a1));
-			{
-				long long t0[2], t1[2];
-				q6_ld<BUF>(a.price, c + u * nw, r0, 16u * lane, a0, z, t0);
-				q6_ld<BUF>(a.price, c + u * nw, r1, 1024u + 16u * lane, a1, z, t1);
-				v0[u].x = t0[0];
-				v0[u].y = t0[1];
-				v1[u].x = t1[0];
-				v1[u].y = t1[1];
-			}
-		}
-#pragma unroll
-		for (int u = 0; u < UNROLL; u++) {
-			const int64_t p[4] = {v0[u][0], v0[u][1], v1[u][0], v1[u][1]};
-			const int64_t di[4] = {d0[u][0], d0[u][1], d1[u][0], d1[u][1]};
-#pragma unroll
-			for (int k = 0; k < 4; k++)
-				if (m[u][k] && p[k] != INT64_MIN)
-					acc += (hge) p[k] * (hge) di[k];
-		}
-	}
-	for (; c < nch; c += nw) {
-		const uint64_t r0 = c * 256 + 2 * lane, r1 = r0 + 128;
-		for (int k = 0; k < 2; k++) {
-			acc += q6_row(a, a.sd[r0 + k], a.disc[r0 + k], a.qty[r0 + k], a.price[r0 + k]);
-			acc += q6_row(a, a.sd[r1 + k], a.disc[r1 + k], a.qty[r1 + k], a.price[r1 + k]);
-		}
-		nlines += 3 * 16;                        // counted as fully read
 	}
 	if (blockIdx.x == 0 && threadIdx.x < (a.n & 255)) {
 		const uint64_t r = nch * 256 + threadIdx.x;
@@ -1009,7 +1110,18 @@ mgdk_tpch_lineitem(uint64_t seed, uint64_t row0, uint64_t n, uint64_t sf_parts, 
 // 16 -- 1.61 vs 1.83 ms on the same box; more, shorter-lived workgroups
 // balance the cascade's uneven per-chunk work across the CUs (64: 1.67,
 // 160-192: 1.68, 512: 1.79 with more chunks left to the scalar tail loop)
-static std::atomic<int> q6_variant{19}, q6_bpc{128};
+// variants 24 / 25 (the default: 24): the buffer-load cascade with 2 / 4
+// chunks in flight reading discount and quantity through their column
+// images (1 or 2 bytes per row instead of 8, Priv::cimg) where the columns
+// have one -- mgdk_q6_fused asks for them, which builds them on the first
+// call per the mgdk_set_colimg_min policy; a column without an image is read
+// raw by the same kernel (k_q6s<U, true, DW, QW>).  Variants below 24 never
+// look at images.  SF100 on MI355X (profiles/q6_images/): 5.39 GB read
+// instead of 10.53; variant 24 at 32 / 64 / 128 WG/CU 1.014 / 0.990 / 1.003 ms,
+// variant 25 1.012 / 1.002 / 1.094 ms, variant 19 at 128 WG/CU 1.645 ms on
+// the same box -- hence 24 at 64 WG/CU.
+constexpr int Q6_IMG_VARIANT = 24;
+static std::atomic<int> q6_variant{Q6_IMG_VARIANT}, q6_bpc{64};
 static thread_local unsigned long long q6_lines = 0;
 // fused Q1 main pass (tools/q1_tune.py, profiles/r01/q1_tune.log)
 static std::atomic<int> q1_layout{MGDK_Q1_LAYOUT}, q1_blocks{MGDK_Q1_BLOCKS};
@@ -1032,6 +1144,23 @@ launch_q6(Q6Args a, int variant, int bpc, hipStream_t st)
 			goto full;
 		}
 		const int64_t *z = (const int64_t *) zbuf;
+		if (variant >= Q6_IMG_VARIANT) {
+			// DW / QW: the widths of the images mgdk_q6_fused got (0: none)
+			const int dw = a.dimg ? a.dw : 0, qw = a.qimg ? a.qw : 0;
+#define Q6I(U, D, Q) hipLaunchKernelGGL((k_q6s<U, true, D, Q>), g, blk, 0, st, a, z)
+#define Q6IW(U) do { switch (dw * 3 + qw) { \
+			case 0: Q6I(U, 0, 0); break; case 1: Q6I(U, 0, 1); break; case 2: Q6I(U, 0, 2); break; \
+			case 3: Q6I(U, 1, 0); break; case 4: Q6I(U, 1, 1); break; case 5: Q6I(U, 1, 2); break; \
+			case 6: Q6I(U, 2, 0); break; case 7: Q6I(U, 2, 1); break; default: Q6I(U, 2, 2); break; } } while (0)
+			if (variant == Q6_IMG_VARIANT)
+				Q6IW(2);
+			else
+				Q6IW(4);
+#undef Q6IW
+#undef Q6I
+			hipLaunchKernelGGL(k_q6_fin, dim3(1), dim3(1024), 0, st, a.parts, g.x, a.out);
+			return;
+		}
 		switch (variant) {
 		case 17: hipLaunchKernelGGL((k_q6s<2>), g, blk, 0, st, a, z); break;
 		case 18: hipLaunchKernelGGL((k_q6s<1>), g, blk, 0, st, a, z); break;
@@ -1105,8 +1234,30 @@ mgdk_q6_fused(mgdk_bat *shipdate, mgdk_bat *discount, mgdk_bat *quantity, mgdk_b
 	a.dlo = dlo;
 	a.dhi = dhi;
 	a.qmax = qmax;
-	a.out = (unsigned long long *) meta_buf();
 	a.parts = nullptr;
+	a.dimg = a.qimg = nullptr;
+	a.dw = a.qw = 0;
+	a.dbase = 0;
+	a.dclo = a.dchi = a.qk = 0;
+	const int variant = q6_variant.load();
+	const bool al = aligned16(a.sd) && aligned16(a.disc) && aligned16(a.qty) && aligned16(a.price);
+	if (variant >= Q6_IMG_VARIANT && al && a.n) {
+		// the images of discount and quantity (built here on their first
+		// use); without one the kernel reads that column raw
+		ColImg im;
+		if (colimg_get(discount, &im)) {
+			a.dimg = im.codes;
+			a.dw = im.width;
+			a.dbase = im.base;
+			q6_code_range(im.base, im.width, dlo, dhi, &a.dclo, &a.dchi);
+		}
+		if (colimg_get(quantity, &im)) {
+			a.qimg = im.codes;
+			a.qw = im.width;
+			a.qk = q6_code_below(im.base, im.width, qmax);
+		}
+	}
+	a.out = (unsigned long long *) meta_buf();
 	hipStream_t st = stream();
 	// out: [0..1] revenue, [2] column lines read by the cascade
 	if (!hip_ok(hipMemsetAsync(a.out, 0, 128, st), "memset"))
@@ -1114,9 +1265,8 @@ mgdk_q6_fused(mgdk_bat *shipdate, mgdk_bat *discount, mgdk_bat *quantity, mgdk_b
 	{
 		ProfScope prof("q6_fused");
 		if (a.n) {
-			bool al = aligned16(a.sd) && aligned16(a.disc) && aligned16(a.qty) && aligned16(a.price);
 			if (al)
-				launch_q6(a, q6_variant.load(), q6_bpc.load(), st);
+				launch_q6(a, variant, q6_bpc.load(), st);
 			else
 				hipLaunchKernelGGL(k_q6_scalar, dim3(grid_for(a.n, 256 * 4, 256 * 16)), dim3(256), 0, st, a);
 		}

@@ -177,6 +177,8 @@ _SIGS = {
     "mgdk_BATunmask": (P, [P]),
     "mgdk_BATorderidx": (C.c_int, [P, C.c_bool]),
     "mgdk_set_fp_parallel_min": (C.c_uint64, [C.c_uint64]),
+    "mgdk_set_colimg_min": (C.c_uint64, [C.c_uint64]),
+    "mgdk_colimg_info": (C.c_int, [P, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "mgdk_BATcalcavg": (C.c_int, [P, P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]),
     "mgdk_BATcheckorderidx": (C.c_bool, [P]),
     "mgdk_OIDXdestroy": (None, [P]),
@@ -739,6 +741,22 @@ def set_fp_parallel_min(rows):
     takes the parallel form (None: never); returns the previous value"""
     init()
     return int(lib().mgdk_set_fp_parallel_min(BUN_NONE if rows is None else int(rows)))
+
+
+def set_colimg_min(rows):
+    """rows from which an int / date / lng column gets a column image (its
+    values minus their minimum in 1 or 2 bytes per row) when a reader asks
+    for one (None: never); returns the previous value"""
+    init()
+    return int(lib().mgdk_set_colimg_min(BUN_NONE if rows is None else int(rows)))
+
+
+def colimg_info(b):
+    """State of b's column image: (0, None, None) unknown, (-1, None, None)
+    ineligible, (1, width, base) ready.  Never builds one."""
+    w, base = C.c_int(0), C.c_int64(0)
+    st = int(lib().mgdk_colimg_info(b.ptr, C.byref(w), C.byref(base)))
+    return (st, int(w.value), int(base.value)) if st == 1 else (st, None, None)
 
 
 def BATorderidx(b, stable=False):
@@ -1331,7 +1349,9 @@ def q6_last_lines():
 def q6_set_variant(variant, blocks_per_cu):
     """Launch variant of the fused Q6 (tuning / tests): 14 = full read (k_q6c),
     16 / 17 / 18 = predicate cascade (k_q6s) with 4 / 2 / 1 chunks in flight, 19 / 20 = the
-    cascade with buffer loads (2 / 4 chunks; the default is 19 at 16 workgroups per CU)."""
+    cascade with buffer loads (2 / 4 chunks), 24 / 25 = that cascade reading discount and
+    quantity through their column images where they have one (2 / 4 chunks; the default is 24
+    at 64 workgroups per CU; see set_colimg_min).  Variants below 24 never use images."""
     lib().mgdk_q6_set_variant(C.c_int(variant), C.c_int(blocks_per_cu))
 
 
