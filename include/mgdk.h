@@ -530,6 +530,36 @@ int mgdk_q1_opatatime(mgdk_bat *shipdate, mgdk_bat *returnflag, mgdk_bat *linest
 		      mgdk_bat *quantity, mgdk_bat *extendedprice, mgdk_bat *discount,
 		      mgdk_bat *tax, int32_t dmax, mgdk_q1row *rows, int maxgroups, int *ngroups);
 
+/* ---- fused select cascade + exact sums (the plan fragment "range / theta
+ *      selects over aligned integer columns, then sum(a) or sum(a * b) over
+ *      the survivors"; Q6 is one instance) -------------------------------- */
+typedef struct mgdk_selpred {
+	mgdk_bat *b;            /* bte / sht / int / lng column, or date / daytime / timestamp on those base types */
+	const void *tl, *th;    /* as BATselect: values of b's type; th NULL = point select */
+	bool li, hi, anti, nil_matches;
+	const char *op;         /* non-NULL: BATthetaselect(b, ., tl, op); th / li / hi / anti / nil_matches ignored */
+} mgdk_selpred;
+typedef struct mgdk_sumexpr { mgdk_bat *a, *b; } mgdk_sumexpr;   /* sum(a) when b == NULL, else sum(a * b) */
+/* c_0 = s; c_i = BATselect(preds[i].b, c_{i-1}, ...) (BATthetaselect when op
+ * is set); *count = BATcount(c_npreds); results[j] = BATsum(TYPE_hge,
+ * BATproject(c, a), skip_nils = true, nil_if_empty = true), or the same over
+ * BATcalcmul(BATproject(c, a), BATproject(c, b), TYPE_hge).  The fused entry
+ * computes this in one pass for 1..4 predicates and 0..4 sums over columns of
+ * 1, 2, 4 or 8 bytes on an integer base type, all of one count and hseqbase,
+ * with s NULL or dense; it returns 0 only when no order of summation could
+ * overflow (count x max|a| x max|b| < 2^127 for every sum), so the wrapped
+ * 128-bit sum is the true one.  Returns 0: done; 1: not applicable, nothing
+ * computed and no error set, the caller runs the operators; -1: error. */
+int mgdk_select_sum_fused(const mgdk_selpred *preds, int npreds, mgdk_bat *s,
+			  const mgdk_sumexpr *sums, int nsums,
+			  void *results /* nsums hge, 16 bytes each */, uint64_t *count);
+/* the same request through the operators; never returns 1 */
+int mgdk_select_sum_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s,
+			      const mgdk_sumexpr *sums, int nsums, void *results, uint64_t *count);
+/* 128-byte lines the calling thread's last fused call read, all columns but the first
+ * predicate's, which is read whole (measurement only; compare mgdk_q6_last_sectors) */
+unsigned long long mgdk_select_sum_last_lines(void);
+
 /* ---- synthetic TPC-H lineitem generated directly in HBM (same values as
  *      oracle/tpch_gen.c); cols: shipdate(date), quantity, extendedprice,
  *      discount, tax (lng), returnflag, linestatus (str, 1-byte offsets) -- */

@@ -196,9 +196,55 @@ q6_opatatime(mgdk_bat *shipdate, mgdk_bat *discount, mgdk_bat *quantity, mgdk_ba
 	return mgdk_BATsum(revenue, MGDK_hge, m, nullptr, true, true);
 }
 
+// the select cascade + sums fragment (mgdk_select_sum_fused) through the
+// operators: selects chained through their candidate lists, one projection
+// per operand, batcalc.* into hge, aggr.sum
+int
+select_sum_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s, const mgdk_sumexpr *sums, int nsums,
+		     void *results, uint64_t *count)
+{
+	Bats t;
+	mgdk_bat *c = s;
+	for (int i = 0; i < npreds; i++) {
+		const mgdk_selpred &p = preds[i];
+		c = t.add(p.op ? mgdk_BATthetaselect(p.b, c, p.tl, p.op)
+			       : mgdk_BATselect(p.b, c, p.tl, p.th, p.li, p.hi, p.anti, p.nil_matches));
+		if (!c)
+			return -1;
+	}
+	if (c == nullptr) {
+		seterr("select_sum: a predicate or a candidate list is required");
+		return -1;
+	}
+	if (count)
+		*count = c->count;
+	for (int j = 0; j < nsums; j++) {
+		if (sums[j].a == nullptr) {
+			seterr("select_sum: a sum needs its first operand");
+			return -1;
+		}
+		mgdk_bat *v = t.add(mgdk_BATproject(c, sums[j].a));
+		if (v && sums[j].b) {
+			mgdk_bat *pb = t.add(mgdk_BATproject(c, sums[j].b));
+			v = pb ? t.add(mgdk_BATcalcmul(v, pb, nullptr, nullptr, MGDK_hge)) : nullptr;
+		}
+		if (!v)
+			return -1;
+		if (mgdk_BATsum((char *) results + 16 * (size_t) j, MGDK_hge, v, nullptr, true, true) < 0)
+			return -1;
+	}
+	return 0;
+}
+
 }  // namespace mgdk
 
 extern "C" {
+
+int mgdk_select_sum_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s, const mgdk_sumexpr *sums,
+			      int nsums, void *results, uint64_t *count)
+{
+	return select_sum_opatatime(preds, npreds, s, sums, nsums, results, count);
+}
 
 // op-at-a-time variants exported for timing the GDK-boundary path
 int mgdk_q6_opatatime(mgdk_bat *shipdate, mgdk_bat *discount, mgdk_bat *quantity, mgdk_bat *price,

@@ -58,6 +58,17 @@ P = C.POINTER(MgdkBat)
 PP = C.POINTER(P)
 
 
+class SelPred(C.Structure):
+    """mgdk_selpred: one BATselect (op NULL) or BATthetaselect of a select cascade."""
+    _fields_ = [("b", P), ("tl", C.c_void_p), ("th", C.c_void_p), ("li", C.c_bool), ("hi", C.c_bool),
+                ("anti", C.c_bool), ("nil_matches", C.c_bool), ("op", C.c_char_p)]
+
+
+class SumExpr(C.Structure):
+    """mgdk_sumexpr: sum(a), or sum(a * b) when b is set."""
+    _fields_ = [("a", P), ("b", P)]
+
+
 class GDKError(RuntimeError):
     pass
 
@@ -232,6 +243,11 @@ _SIGS = {
                                     C.c_int64, C.c_void_p]),
     "mgdk_q1_opatatime": (C.c_int, [P, P, P, P, P, P, P, C.c_int32, C.POINTER(Q1Row), C.c_int,
                                     C.POINTER(C.c_int)]),
+    "mgdk_select_sum_fused": (C.c_int, [C.POINTER(SelPred), C.c_int, P, C.POINTER(SumExpr), C.c_int,
+                                        C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mgdk_select_sum_opatatime": (C.c_int, [C.POINTER(SelPred), C.c_int, P, C.POINTER(SumExpr), C.c_int,
+                                            C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mgdk_select_sum_last_lines": (C.c_ulonglong, []),
     "mgdk_tpch_lineitem": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, PP]),
     "mgdk_gen_window_column": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, PP, PP]),
     "mgdk_BAThashpartition": (C.c_int, [PP, C.c_void_p, C.c_int, C.c_void_p]),
@@ -1360,6 +1376,60 @@ def q6_opatatime(shipdate, discount, quantity, price, d0, d1, dlo, dhi, qmax):
     _chk(lib().mgdk_q6_opatatime(shipdate.ptr, discount.ptr, quantity.ptr, price.ptr, d0, d1, dlo,
                                  dhi, qmax, C.cast(out, C.c_void_p)))
     return hge_to_int(out)
+
+
+def select_sum(preds, sums, s=None, fused=True, fallback=True):
+    """A select cascade and exact sums over its survivors (mgdk_select_sum_fused).
+
+    preds: (b, tl, th, li, hi, anti[, nil_matches]) for a BATselect or
+    (b, val, op) for a BATthetaselect, each taking the previous one's result
+    as its candidate list (the first one s); sums: (a, b) for sum(a * b),
+    (a, None) or a for sum(a), over the last candidate list, as hge.
+    Returns ([int, or None for nil], count, used_fused).  fused=True tries
+    the one-pass kernel; when it is not applicable the operators run instead
+    (used_fused False) -- or, with fallback=False, None is returned and
+    nothing was computed.  fused=False runs the operators."""
+    keep = []
+    npr, ns = len(preds), len(sums)
+    cp = (SelPred * max(1, npr))()
+    for i, p in enumerate(preds):
+        b = p[0]
+        cp[i].b = b.ptr
+        if len(p) == 3:
+            cp[i].tl = _valptr(b.ttype, p[1], keep)
+            cp[i].op = p[2].encode()
+        else:
+            cp[i].tl = _valptr(b.ttype, p[1], keep)
+            cp[i].th = _valptr(b.ttype, p[2], keep)
+            cp[i].li, cp[i].hi, cp[i].anti = bool(p[3]), bool(p[4]), bool(p[5])
+            cp[i].nil_matches = bool(p[6]) if len(p) > 6 else False
+    cs = (SumExpr * max(1, ns))()
+    for j, e in enumerate(sums):
+        a, b = e if isinstance(e, (tuple, list)) else (e, None)
+        cs[j].a = a.ptr
+        if b is not None:
+            cs[j].b = b.ptr
+    out = (C.c_uint64 * (2 * max(1, ns)))()
+    cnt = C.c_uint64()
+    args = (cp, npr, _p(s), cs, ns, C.cast(out, C.c_void_p), C.byref(cnt))
+    used = False
+    if fused:
+        rc = lib().mgdk_select_sum_fused(*args)
+        if rc < 0:
+            raise _err()
+        used = rc == 0
+        if not used and not fallback:
+            return None
+    if not used:
+        _chk(lib().mgdk_select_sum_opatatime(*args))
+    vals = [hge_to_int(out[2 * j:2 * j + 2]) for j in range(ns)]
+    return [None if v == NIL[TYPE_hge] else v for v in vals], int(cnt.value), used
+
+
+def select_sum_last_lines():
+    """128-B lines the last fused select_sum on this thread read of every
+    column but the first predicate's (which is read whole)."""
+    return int(lib().mgdk_select_sum_last_lines())
 
 
 def q1_fused(cols, dmax, maxgroups=64, fused=True):
