@@ -311,6 +311,13 @@ def test_convert_parity(gdk, ora, st, dt, s1, s2, prec):
     db, ob = mkpair(gdk, ora, st, b)
     both_or_error(lambda: gdk.BATconvert(db, None, T, s1, s2, prec), lambda: ora.BATconvert(ob, None, T, s1, s2, prec),
                   w + " small")
+    if (st, dt) == ("dbl", "oid"):
+        # every call above ends in "overflow in conversion of <negative> to
+        # oid": compare values on the non-negative, in-range part
+        pos = a[(a >= 0) & (a < 2.0 ** 62) | np.isnan(a)]
+        assert np.isnan(pos).any() and (pos > 2.0 ** 52).any() and (pos % 1 != 0).any()
+        dp, op_ = mkpair(gdk, ora, st, pos)
+        same(gdk.BATconvert(dp, None, T, s1, s2, prec), ora.BATconvert(op_, None, T, s1, s2, prec), w + " non-negative")
 
 
 @pytest.mark.gpu
@@ -347,6 +354,9 @@ def test_calcnot_parity(gdk, ora, tp):
         both_or_error(lambda: gdk.BATcalcnot(d), lambda: ora.BATcalcnot(o), "not overflow " + tp)
 
 
+# the two ->bte entries at the end are combinations the operators refuse
+# (quotient narrower than the dividend, remainder narrower than both
+# operands): all their calls compare a "not supported" message, no values
 DIVMOD = [("/", "int", "int", "int"), ("/", "lng", "int", "dbl"), ("/", "int", "dbl", "dbl"), ("/", "flt", "int", "flt"),
           ("/", "hge", "lng", "hge"), ("/", "dbl", "flt", "dbl"), ("/", "bte", "flt", "flt"), ("/", "sht", "int", "lng"),
           ("%", "int", "int", "int"), ("%", "lng", "bte", "bte"), ("%", "hge", "int", "int"), ("%", "int", "flt", "flt"),

@@ -207,6 +207,26 @@ def test_calc(gdk, ora, op, t1, t2, tp):
     assert [int(x) for x in got] == [int(x) for x in want]
 
 
+def test_calc_narrow_result_values(gdk, ora):
+    """sht * bte -> sht on a column that fits (test_calc's own sht * bte
+    column overflows, so only its message is compared there): values
+    compared, up to +-32767 = +-32767 * 1 and +-32766 = +-258 * 127, with
+    nils."""
+    r = rng(32)
+    n = 20_000
+    b = r.integers(-100, 101, n)
+    lim = 32767 // np.maximum(np.abs(b), 1)
+    a = r.integers(-lim, lim + 1)
+    a = with_nils(a.astype(np.int16), gdk.NIL[gdk.TYPE_sht], 0.02, r)
+    b = with_nils(b.astype(np.int8), gdk.NIL[gdk.TYPE_bte], 0.02, r)
+    a[:4] = [32767, -32767, -258, 258]
+    b[:4] = [1, 1, -127, -127]
+    got = gdk.BATcalcmul(mk(gdk, gdk.TYPE_sht, a), mk(gdk, gdk.TYPE_bte, b), gdk.TYPE_sht).values()
+    want = ora.BATcalc("*", omk(ora, ora.TYPE_sht, a), omk(ora, ora.TYPE_bte, b), ora.TYPE_sht).values()
+    assert [int(x) for x in got] == [int(x) for x in want]
+    assert all(v in want for v in (32767, -32767, 32766, -32766, -32768))
+
+
 def test_calc_overflow_matches(gdk, ora):
     a = np.array([1, 5, 2**30, 7, 2**30], np.int32)
     ga, oa = mk(gdk, gdk.TYPE_int, a), omk(ora, ora.TYPE_int, a)
@@ -234,10 +254,12 @@ def test_calc_cst_and_candidates(gdk, ora):
 
 @pytest.mark.parametrize("n", [1, 2, 7, 100_003])
 def test_calc_pair_path(gdk, ora, n):
-    """The paired kernel (two elements per lane, 16-byte loads / stores) for
-    dense 8 / 16-byte operands: odd counts, sliced operands (element 0 on an
-    8-byte boundary -> the single-element kernel), hge x lng -> hge (Q1's
-    charge), constants, nils, and an overflow at an odd position."""
+    """The typed 8- and 16-byte loaders of k_calc_d (WA / WB = 8, 16) for
+    dense lng and hge operands: counts of 1, 2, 7 and past one workgroup,
+    operands sliced at rows 0, 1 and 2 (so an lng column starts on and off a
+    16-byte boundary), lng x lng -> lng and -> hge (the unchecked form), hge x
+    lng -> hge (Q1's charge), a constant first operand, nils, and an overflow
+    at row 5."""
     r = rng(43)
     a = with_nils(r.integers(-10**6, 10**6, n + 3).astype(np.int64), gdk.NIL[gdk.TYPE_lng], 0.03, r)
     b = with_nils(r.integers(-10**6, 10**6, n + 3).astype(np.int64), gdk.NIL[gdk.TYPE_lng], 0.03, r)
