@@ -504,6 +504,10 @@ int mgdk_q6_fused(mgdk_bat *shipdate, mgdk_bat *discount, mgdk_bat *quantity,
  * when one of the line's rows passed the earlier predicates; shipdate is
  * read whole).  0 after a full-read launch variant.  Measurement only. */
 unsigned long long mgdk_q6_last_sectors(void);
+/* All the bytes that launch asked for: shipdate at the width it was read at
+ * (2 or 1 through a column image, else 4) times the rows, plus 128 times the
+ * lines above; 28 bytes per row after a full-read variant.  Measurement only. */
+unsigned long long mgdk_q6_last_bytes(void);
 typedef struct mgdk_q1row {
 	uint8_t returnflag, linestatus, _pad[6];   /* str heap offsets */
 	int64_t sum_qty[2], sum_base_price[2], sum_disc_price[2], sum_charge[2]; /* hge lo,hi */

@@ -155,6 +155,10 @@ struct Q6Args {
 	int64_t dbase;             // discount = dbase + code
 	uint32_t dclo, dchi, qk;   // dclo <= discount code <= dchi, quantity code < qk
 	int dw, qw;                // image widths (host side: picks the instantiation)
+	// the wide variants (q6w::k_q6s) also read shipdate through its image
+	const void *simg;
+	uint32_t sclo, schi;       // sclo <= shipdate code <= schi
+	int sw;
 };
 
 // one workgroup's exact revenue and (k_q6s) line count: written once per
@@ -605,6 +609,280 @@ k_q6s(Q6Args a, const int64_t *zline)
 	}
 	q6_publish(a, acc, nlines);
 }
+
+// The cascade with a wider row-to-lane mapping (variants 26 / 27): a wave
+// owns a 512-row chunk and lane l its rows 8l .. 8l+7, and shipdate is read
+// through a column image too (SW = its width, 0 = the raw int column).  A
+// lane then loads the 8 codes of a 1- / 2-byte image with one 8- / 16-byte
+// load, and a raw lng column with four 16-byte buffer loads, one per row
+// pair and each guarded by its own pair: 7 wave loads per 512 rows with
+// three images where k_q6s above issues 16.  Which lines are fetched does
+// not change: an image line (16 / 8 lanes) or a lng line (2 lanes) is read
+// exactly when one of its rows is still in.  The date predicate is compared
+// in the code domain like the other two (the nil code lies above every
+// bound).  UNROLL = 1 (variant 26) takes one chunk at a time and keeps the
+// next chunk's shipdates under way meanwhile; UNROLL = 2 (variant 27) has
+// two chunks in flight per stage like k_q6s<2> above, and runs the chunks
+// its loop leaves over one at a time.  Same kernel name, so profiles find
+// it as k_q6s.
+namespace q6w {
+
+constexpr unsigned CH = 512;
+typedef unsigned int u2 __attribute__((ext_vector_type(2)));
+
+// code k (0 .. 7) of the lane's 8 rows from the words of its image load
+template <int W>
+__device__ __forceinline__ uint32_t
+code(const uint32_t *w, int k)
+{
+	if constexpr (W == 1)
+		return (w[k >> 2] >> (8 * (k & 3))) & 0xffu;
+	else
+		return (w[k >> 1] >> (16 * (k & 1))) & 0xffffu;
+}
+
+// the lane's 8 codes: one buffer load of 8 W bytes (w[0 .. 2 W - 1]); a dead
+// lane's out-of-range offset gives zeros with no memory access
+template <int W>
+__device__ __forceinline__ void
+ldimg(const void *img, uint64_t chunk, unsigned lane, bool live, uint32_t *w)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__) && !defined(__gfx942__)
+#error "q6w::ldimg: buffer descriptor word 3 is laid out for gfx942 / gfx950 only"
+#endif
+	__amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *) ((const char *) img + chunk * (CH * W)),
+								      (short) 0, CH * W, 0x00020000);
+	const unsigned off = live ? 8u * W * lane : 0x80000000u;
+	if constexpr (W == 1) {
+		const u2 v = __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, 0);
+		w[0] = v.x;
+		w[1] = v.y;
+	} else {
+		const q6u4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
+		w[0] = v.x;
+		w[1] = v.y;
+		w[2] = v.z;
+		w[3] = v.w;
+	}
+}
+
+// the lane's 8 rows of a raw lng column: row pair j is loaded when one of
+// its rows is in m (bit k = row k)
+__device__ __forceinline__ void
+ldraw(const int64_t *col, uint64_t chunk, unsigned lane, uint32_t m, long long *v)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__) && !defined(__gfx942__)
+#error "q6w::ldraw: buffer descriptor word 3 is laid out for gfx942 / gfx950 only"
+#endif
+	__amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *) (col + chunk * CH), (short) 0, CH * 8,
+								      0x00020000);
+#pragma unroll
+	for (int j = 0; j < 4; j++) {
+		const unsigned off = ((m >> (2 * j)) & 3u) ? 64u * lane + 16u * j : 0x80000000u;
+		const q6u4 t = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
+		v[2 * j] = (long long) (((unsigned long long) t.y << 32) | t.x);
+		v[2 * j + 1] = (long long) (((unsigned long long) t.w << 32) | t.z);
+	}
+}
+
+// 128-B lines the loads of one column touch in a chunk, from the ballot of
+// the lanes with a live row: 16 lanes per line of a 1-byte image, 8 of a
+// 2-byte image, 2 of a raw lng column (W = 0)
+template <int W>
+__device__ __forceinline__ uint32_t
+lines(uint64_t b)
+{
+	if constexpr (W == 1) {
+		return ((b & 0xffffull) != 0) + ((b & 0xffff0000ull) != 0) + ((b & 0xffff00000000ull) != 0) +
+		       ((b >> 48) != 0);
+	} else if constexpr (W == 2) {
+		b |= b >> 1;
+		b |= b >> 2;
+		b |= b >> 4;
+		return (uint32_t) __popcll(b & 0x0101010101010101ull);
+	} else {
+		b |= b >> 1;
+		return (uint32_t) __popcll(b & 0x5555555555555555ull);
+	}
+}
+
+// the lane's 8 shipdates of a chunk as loaded: 4 / 2 words of codes from a
+// 2- / 1-byte image, 8 raw dates without one (read whole, never guarded)
+template <int SW>
+__device__ __forceinline__ void
+ldsd(const Q6Args &a, uint64_t chunk, unsigned lane, uint32_t *w)
+{
+	typedef int32_t i4 __attribute__((ext_vector_type(4)));
+	const uint64_t r = chunk * CH + 8 * lane;
+	if constexpr (SW == 2) {
+		const q6u4 t = __builtin_nontemporal_load((const q6u4 *) ((const uint16_t *) a.simg + r));
+		w[0] = t.x;
+		w[1] = t.y;
+		w[2] = t.z;
+		w[3] = t.w;
+	} else if constexpr (SW == 1) {
+		const u2 t = __builtin_nontemporal_load((const u2 *) ((const uint8_t *) a.simg + r));
+		w[0] = t.x;
+		w[1] = t.y;
+	} else {
+		const i4 t0 = __builtin_nontemporal_load((const i4 *) (a.sd + r));
+		const i4 t1 = __builtin_nontemporal_load((const i4 *) (a.sd + r + 4));
+		w[0] = (uint32_t) t0.x;
+		w[1] = (uint32_t) t0.y;
+		w[2] = (uint32_t) t0.z;
+		w[3] = (uint32_t) t0.w;
+		w[4] = (uint32_t) t1.x;
+		w[5] = (uint32_t) t1.y;
+		w[6] = (uint32_t) t1.z;
+		w[7] = (uint32_t) t1.w;
+	}
+}
+
+// bit k: the date of row k passes
+template <int SW>
+__device__ __forceinline__ uint32_t
+sdmask(const Q6Args &a, const uint32_t *w)
+{
+	uint32_t m = 0;
+#pragma unroll
+	for (int k = 0; k < 8; k++) {
+		if constexpr (SW != 0) {
+			const uint32_t sc = code<SW>(w, k);
+			m |= (uint32_t) (sc >= a.sclo && sc <= a.schi) << k;
+		} else {
+			const int32_t sd = (int32_t) w[k];
+			m |= (uint32_t) (sd != INT32_MIN && sd >= a.d0 && sd < a.d1) << k;
+		}
+	}
+	return m;
+}
+
+constexpr uint64_t NOCHUNK = ~(uint64_t) 0;
+
+// the cascade over U chunks (c, c + nw, ...), all loads of one column in
+// flight together; m[u] bit k: row 8 lane + k of chunk u is still in.
+// PF (U = 1): the chunk's shipdates are in pf already, and those of chunk
+// cn (if any) are loaded into pf behind the discount load, so that the one
+// column read whole streams on through the dependent stages.
+template <int U, int SW, int DW, int QW, bool PF>
+__device__ __forceinline__ void
+chunks(const Q6Args &a, uint64_t c, uint64_t nw, unsigned lane, hge &acc, uint32_t &nlines, uint32_t *pf, uint64_t cn)
+{
+	static_assert(!PF || U == 1, "the shipdate prefetch runs one chunk at a time");
+	uint32_t sw[U][8], dcw[U][4], qcw[U][4], m[U];
+	long long dv[U][8], v[U][8];
+	if constexpr (PF) {
+		m[0] = sdmask<SW>(a, pf);
+	} else {
+#pragma unroll
+		for (int u = 0; u < U; u++)
+			ldsd<SW>(a, c + u * nw, lane, sw[u]);
+#pragma unroll
+		for (int u = 0; u < U; u++)
+			m[u] = sdmask<SW>(a, sw[u]);
+	}
+	// discount where the date holds
+#pragma unroll
+	for (int u = 0; u < U; u++) {
+		nlines += lines<DW>(__ballot(m[u] != 0));
+		if constexpr (DW != 0)
+			ldimg<DW>(a.dimg, c + u * nw, lane, m[u] != 0, dcw[u]);
+		else
+			ldraw(a.disc, c + u * nw, lane, m[u], dv[u]);
+	}
+	if constexpr (PF) {
+		if (cn != NOCHUNK)
+			ldsd<SW>(a, cn, lane, pf);
+	}
+#pragma unroll
+	for (int u = 0; u < U; u++) {
+		uint32_t ok = 0;
+#pragma unroll
+		for (int k = 0; k < 8; k++) {
+			if constexpr (DW != 0) {
+				const uint32_t dc = code<DW>(dcw[u], k);
+				ok |= (uint32_t) (dc >= a.dclo && dc <= a.dchi) << k;
+			} else {
+				ok |= (uint32_t) (dv[u][k] != INT64_MIN && dv[u][k] >= a.dlo && dv[u][k] <= a.dhi) << k;
+			}
+		}
+		m[u] &= ok;
+	}
+	// quantity where date and discount hold
+#pragma unroll
+	for (int u = 0; u < U; u++) {
+		nlines += lines<QW>(__ballot(m[u] != 0));
+		if constexpr (QW != 0)
+			ldimg<QW>(a.qimg, c + u * nw, lane, m[u] != 0, qcw[u]);
+		else
+			ldraw(a.qty, c + u * nw, lane, m[u], v[u]);
+	}
+#pragma unroll
+	for (int u = 0; u < U; u++) {
+		uint32_t ok = 0;
+#pragma unroll
+		for (int k = 0; k < 8; k++) {
+			if constexpr (QW != 0)
+				ok |= (uint32_t) (code<QW>(qcw[u], k) < a.qk) << k;
+			else
+				ok |= (uint32_t) (v[u][k] != INT64_MIN && v[u][k] < a.qmax) << k;
+		}
+		m[u] &= ok;
+	}
+	// extendedprice where all three hold
+#pragma unroll
+	for (int u = 0; u < U; u++) {
+		nlines += lines<0>(__ballot(m[u] != 0));
+		ldraw(a.price, c + u * nw, lane, m[u], v[u]);
+	}
+#pragma unroll
+	for (int u = 0; u < U; u++) {
+#pragma unroll
+		for (int k = 0; k < 8; k++) {
+			int64_t di;
+			if constexpr (DW != 0)
+				di = a.dbase + (int64_t) code<DW>(dcw[u], k);
+			else
+				di = dv[u][k];
+			if (((m[u] >> k) & 1u) && v[u][k] != INT64_MIN)
+				acc += (hge) v[u][k] * (hge) di;
+		}
+	}
+}
+
+template <int UNROLL, int SW, int DW, int QW>
+__global__ __launch_bounds__(256) void
+k_q6s(Q6Args a)
+{
+	hge acc = 0;
+	uint32_t nlines = 0;
+	const unsigned lane = __lane_id();
+	const uint64_t nch = a.n / CH;
+	const uint64_t nw = (uint64_t) gridDim.x * (blockDim.x / 64);
+	// wave-uniform for the compiler, as in k_q6s above
+	uint64_t c = (uint64_t) blockIdx.x * (blockDim.x / 64) + (unsigned) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
+	if constexpr (UNROLL == 1) {
+		// one chunk at a time, the next one's shipdates already under way
+		uint32_t pf[8];
+		if (c < nch)
+			ldsd<SW>(a, c, lane, pf);
+		for (; c < nch; c += nw)
+			chunks<1, SW, DW, QW, true>(a, c, nw, lane, acc, nlines, pf, c + nw < nch ? c + nw : NOCHUNK);
+	} else {
+		for (; c + (UNROLL - 1) * nw < nch; c += UNROLL * nw)
+			chunks<UNROLL, SW, DW, QW, false>(a, c, nw, lane, acc, nlines, nullptr, NOCHUNK);
+		for (; c < nch; c += nw)
+			chunks<1, SW, DW, QW, false>(a, c, nw, lane, acc, nlines, nullptr, NOCHUNK);
+	}
+	// the rows past the last full chunk, from the raw columns
+	if (blockIdx.x == 0) {
+		for (uint64_t r = nch * CH + threadIdx.x; r < a.n; r += blockDim.x)
+			acc += q6_row(a, a.sd[r], a.disc[r], a.qty[r], a.price[r]);
+	}
+	q6_publish(a, acc, nlines);
+}
+
+}  // namespace q6w
 
 __global__ __launch_bounds__(256) void
 k_q6_scalar(Q6Args a)
@@ -1120,13 +1398,25 @@ mgdk_tpch_lineitem(uint64_t seed, uint64_t row0, uint64_t n, uint64_t sf_parts, 
 // instead of 10.53; variant 24 at 32 / 64 / 128 WG/CU 1.014 / 0.990 / 1.003 ms,
 // variant 25 1.012 / 1.002 / 1.094 ms, variant 19 at 128 WG/CU 1.645 ms on
 // the same box -- hence 24 at 64 WG/CU.
-constexpr int Q6_IMG_VARIANT = 24;
-static std::atomic<int> q6_variant{Q6_IMG_VARIANT}, q6_bpc{64};
-static thread_local unsigned long long q6_lines = 0;
+// variants 26 / 27 (the default: 26): the same cascade with the wide
+// row-to-lane mapping (q6w::k_q6s: 512-row chunks, 8 rows per lane; 26 one
+// chunk at a time with the next chunk's shipdates prefetched, 27 two chunks
+// in flight) and shipdate read through its image as well -- 2 bytes per row
+// for any date column spanning up to 65534 codes, 6.99 B/row = 4.19 GB at
+// SF100.  Variants below 26 neither ask for nor use a shipdate image.
+// profiles/q6_dates/sweep.log, same box and process: variant 24 at 64 WG/CU
+// 0.992 ms; one chunk at a time without the prefetch 0.801 ms, with it
+// 0.690 / 0.688 / 0.688 ms at 32 / 64 / 96 WG/CU (a second chunk of
+// prefetch distance: 0.689), two chunks in flight 0.709 / 0.702 / 0.709 ms
+// -- hence 26 at 64 WG/CU.
+constexpr int Q6_IMG_VARIANT = 24, Q6_WIDE_VARIANT = 26;
+static std::atomic<int> q6_variant{Q6_WIDE_VARIANT}, q6_bpc{64};
+static thread_local unsigned long long q6_lines = 0, q6_bytes = 0;
 // fused Q1 main pass (tools/q1_tune.py, profiles/r01/q1_tune.log)
 static std::atomic<int> q1_layout{MGDK_Q1_LAYOUT}, q1_blocks{MGDK_Q1_BLOCKS};
 
-static void
+// true: a cascade ran (shipdate whole + the counted lines were read)
+static bool
 launch_q6(Q6Args a, int variant, int bpc, hipStream_t st)
 {
 	const int v7 = variant & 7;
@@ -1134,7 +1424,7 @@ launch_q6(Q6Args a, int variant, int bpc, hipStream_t st)
 		const uint32_t nb = 256u * (unsigned) bpc;
 		a.parts = (Q6Part *) scratch((size_t) nb * sizeof(Q6Part));
 		if (a.parts == nullptr)
-			return;
+			return false;
 	}
 	if (variant >= 16) {                 // predicate cascade (k_q6s)
 		dim3 g(256u * (unsigned) bpc), blk(256);
@@ -1144,6 +1434,24 @@ launch_q6(Q6Args a, int variant, int bpc, hipStream_t st)
 			goto full;
 		}
 		const int64_t *z = (const int64_t *) zbuf;
+		if (variant >= Q6_WIDE_VARIANT) {
+			// SW / DW / QW: the widths of the images mgdk_q6_fused got (0: none)
+			const int sw = a.simg ? a.sw : 0, dw = a.dimg ? a.dw : 0, qw = a.qimg ? a.qw : 0;
+#define Q6W(U, S, D, Q) hipLaunchKernelGGL((q6w::k_q6s<U, S, D, Q>), g, blk, 0, st, a)
+#define Q6WQ(U, S, D) do { if (qw == 0) Q6W(U, S, D, 0); else if (qw == 1) Q6W(U, S, D, 1); else Q6W(U, S, D, 2); } while (0)
+#define Q6WD(U, S) do { if (dw == 0) Q6WQ(U, S, 0); else if (dw == 1) Q6WQ(U, S, 1); else Q6WQ(U, S, 2); } while (0)
+#define Q6WS(U) do { if (sw == 0) Q6WD(U, 0); else if (sw == 1) Q6WD(U, 1); else Q6WD(U, 2); } while (0)
+			if (variant == Q6_WIDE_VARIANT)
+				Q6WS(1);
+			else
+				Q6WS(2);
+#undef Q6WS
+#undef Q6WD
+#undef Q6WQ
+#undef Q6W
+			hipLaunchKernelGGL(k_q6_fin, dim3(1), dim3(1024), 0, st, a.parts, g.x, a.out);
+			return true;
+		}
 		if (variant >= Q6_IMG_VARIANT) {
 			// DW / QW: the widths of the images mgdk_q6_fused got (0: none)
 			const int dw = a.dimg ? a.dw : 0, qw = a.qimg ? a.qw : 0;
@@ -1159,7 +1467,7 @@ launch_q6(Q6Args a, int variant, int bpc, hipStream_t st)
 #undef Q6IW
 #undef Q6I
 			hipLaunchKernelGGL(k_q6_fin, dim3(1), dim3(1024), 0, st, a.parts, g.x, a.out);
-			return;
+			return true;
 		}
 		switch (variant) {
 		case 17: hipLaunchKernelGGL((k_q6s<2>), g, blk, 0, st, a, z); break;
@@ -1169,7 +1477,7 @@ launch_q6(Q6Args a, int variant, int bpc, hipStream_t st)
 		default: hipLaunchKernelGGL((k_q6s<4>), g, blk, 0, st, a, z); break;
 		}
 		hipLaunchKernelGGL(k_q6_fin, dim3(1), dim3(1024), 0, st, a.parts, g.x, a.out);
-		return;
+		return true;
 	}
 full:
 	const bool nt = (variant & 8) != 0;
@@ -1188,6 +1496,7 @@ full:
 #undef Q6L
 	if (v >= 3)
 		hipLaunchKernelGGL(k_q6_fin, dim3(1), dim3(1024), 0, st, a.parts, g.x, a.out);
+	return false;
 }
 
 int mgdk_q6_fused(mgdk_bat *shipdate, mgdk_bat *discount, mgdk_bat *quantity, mgdk_bat *extendedprice,
@@ -1235,10 +1544,10 @@ mgdk_q6_fused(mgdk_bat *shipdate, mgdk_bat *discount, mgdk_bat *quantity, mgdk_b
 	a.dhi = dhi;
 	a.qmax = qmax;
 	a.parts = nullptr;
-	a.dimg = a.qimg = nullptr;
-	a.dw = a.qw = 0;
+	a.dimg = a.qimg = a.simg = nullptr;
+	a.dw = a.qw = a.sw = 0;
 	a.dbase = 0;
-	a.dclo = a.dchi = a.qk = 0;
+	a.dclo = a.dchi = a.qk = a.sclo = a.schi = 0;
 	const int variant = q6_variant.load();
 	const bool al = aligned16(a.sd) && aligned16(a.disc) && aligned16(a.qty) && aligned16(a.price);
 	if (variant >= Q6_IMG_VARIANT && al && a.n) {
@@ -1256,9 +1565,17 @@ mgdk_q6_fused(mgdk_bat *shipdate, mgdk_bat *discount, mgdk_bat *quantity, mgdk_b
 			a.qw = im.width;
 			a.qk = q6_code_below(im.base, im.width, qmax);
 		}
+		// sd >= d0 && sd < d1 as a code range over [d0, d1 - 1] (in 64
+		// bits: d1 may be the smallest int)
+		if (variant >= Q6_WIDE_VARIANT && colimg_get(shipdate, &im)) {
+			a.simg = im.codes;
+			a.sw = im.width;
+			q6_code_range(im.base, im.width, d0, (int64_t) d1 - 1, &a.sclo, &a.schi);
+		}
 	}
 	a.out = (unsigned long long *) meta_buf();
 	hipStream_t st = stream();
+	bool cascade = false;
 	// out: [0..1] revenue, [2] column lines read by the cascade
 	if (!hip_ok(hipMemsetAsync(a.out, 0, 128, st), "memset"))
 		return -1;
@@ -1266,7 +1583,7 @@ mgdk_q6_fused(mgdk_bat *shipdate, mgdk_bat *discount, mgdk_bat *quantity, mgdk_b
 		ProfScope prof("q6_fused");
 		if (a.n) {
 			if (al)
-				launch_q6(a, variant, q6_bpc.load(), st);
+				cascade = launch_q6(a, variant, q6_bpc.load(), st);
 			else
 				hipLaunchKernelGGL(k_q6_scalar, dim3(grid_for(a.n, 256 * 4, 256 * 16)), dim3(256), 0, st, a);
 		}
@@ -1276,6 +1593,7 @@ mgdk_q6_fused(mgdk_bat *shipdate, mgdk_bat *discount, mgdk_bat *quantity, mgdk_b
 		return -1;
 	memcpy(revenue, h, 16);
 	q6_lines = h[2];
+	q6_bytes = cascade ? a.n * (uint64_t) (a.simg ? a.sw : 4) + 128 * h[2] : a.n * 28;
 	return 0;
 }
 
@@ -1286,6 +1604,15 @@ extern "C" unsigned long long
 mgdk_q6_last_sectors(void)
 {
 	return q6_lines;
+}
+
+// all the bytes the calling thread's last fused Q6 asked for: shipdate at
+// the width it was read at (its image's, or 4) times the rows plus the 128-B
+// lines above; all four columns for a full-read variant
+extern "C" unsigned long long
+mgdk_q6_last_bytes(void)
+{
+	return q6_bytes;
 }
 
 int

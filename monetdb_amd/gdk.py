@@ -1362,12 +1362,25 @@ def q6_last_lines():
     return int(f())
 
 
+def q6_last_bytes():
+    """All the bytes the last q6_fused on this thread asked for: shipdate at the width it
+    was read at (its image's, or 4) times the rows, plus 128 * q6_last_lines(); 28 per row
+    for a full-read variant."""
+    f = lib().mgdk_q6_last_bytes
+    f.restype = C.c_ulonglong
+    return int(f())
+
+
 def q6_set_variant(variant, blocks_per_cu):
     """Launch variant of the fused Q6 (tuning / tests): 14 = full read (k_q6c),
     16 / 17 / 18 = predicate cascade (k_q6s) with 4 / 2 / 1 chunks in flight, 19 / 20 = the
     cascade with buffer loads (2 / 4 chunks), 24 / 25 = that cascade reading discount and
-    quantity through their column images where they have one (2 / 4 chunks; the default is 24
-    at 64 workgroups per CU; see set_colimg_min).  Variants below 24 never use images."""
+    quantity through their column images where they have one (256-row chunks, 2 / 4 in
+    flight), 26 / 27 = the cascade over 512-row chunks with 8 rows per lane, reading shipdate
+    through its column image as well (26: one chunk at a time with the next chunk's shipdates
+    prefetched, 27: 2 chunks in flight; the default is 26 at 64 workgroups per CU; see
+    set_colimg_min).  Variants below 24 never use images, variants below 26 never ask for a
+    shipdate image."""
     lib().mgdk_q6_set_variant(C.c_int(variant), C.c_int(blocks_per_cu))
 
 

@@ -70,10 +70,11 @@ def config2_q6(sf=10):
     args = (cols["shipdate"], cols["discount"], cols["quantity"], cols["extendedprice"],
             mk(1994, 1, 1), mk(1995, 1, 1), 5, 7, 2400)
     _, wall, kms = timed(lambda: gdk.q6_fused(*args), kernels=("q6_fused",))
-    # the fused Q6 is a predicate cascade: it reads shipdate whole and only
-    # the 128-B lines of the other columns that hold a qualifying row
+    # the fused Q6 is a predicate cascade: it reads shipdate whole (through its
+    # 2-byte column image where it has one) and only the 128-B lines of the
+    # other columns that hold a qualifying row
     lines = gdk.q6_last_lines()
-    fused = entry(rows, rows * 4 + lines * 128 if lines else rows * 28, wall, kms, bytes_full_read=rows * 28,
+    fused = entry(rows, gdk.q6_last_bytes(), wall, kms, bytes_full_read=rows * 28,
                   kernel="k_q6s" if lines else "k_q6c")
     _, wall2, kms2 = timed(lambda: gdk.q6_opatatime(*args), reps=3,
                            kernels=("select", "project", "calc", "sum"))

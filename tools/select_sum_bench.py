@@ -45,7 +45,7 @@ def main():
     preds = [(c["shipdate"], d0, d1, True, False, False), (c["discount"], 5, 7, True, True, False),
              (c["quantity"], 2400, "<")]
     sums = [(c["extendedprice"], c["discount"])]
-    first_bytes = n * 4                  # shipdate, read whole by both fused kernels
+    first_bytes = n * 4                  # shipdate, read whole and raw by the general kernel
 
     def general():
         vals, _, used = gdk.select_sum(preds, sums, fused=True)
@@ -57,7 +57,7 @@ def main():
 
     def q6():
         r = gdk.q6_fused(c["shipdate"], c["discount"], c["quantity"], c["extendedprice"], d0, d1, 5, 7, 2400)
-        return r, first_bytes + 128 * gdk.q6_last_lines()
+        return r, gdk.q6_last_bytes()
 
     legs = {"select_sum_fused": general, "select_sum_opatatime": operators, "q6_fused": q6}
     results, nbytes, ms = {}, {}, {k: [] for k in legs}
