@@ -564,6 +564,58 @@ int mgdk_select_sum_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s
  * predicate's, which is read whole (measurement only; compare mgdk_q6_last_sectors) */
 unsigned long long mgdk_select_sum_last_lines(void);
 
+/* ---- fused select cascade + GROUP BY sums (the grouped sibling: "selects,
+ *      GROUP BY one or two one-byte keys, exact hge sums of columns or of
+ *      products of (constant +- column) factors, counts"; Q1 is one
+ *      instance) --------------------------------------------------------- */
+typedef struct mgdk_gsfactor {
+	mgdk_bat *b;
+	char op;                /* 0: b; '+': cst + b; '-': cst - b (BATcalccstadd / BATcalccstsub into lng) */
+	int64_t cst;
+} mgdk_gsfactor;
+typedef struct mgdk_gsumexpr { mgdk_gsfactor f[3]; int nf; } mgdk_gsumexpr;   /* f[0] * f[1] * f[2], into hge from the left */
+typedef struct mgdk_gsgroup {
+	mgdk_oid first;         /* oid of the group's first surviving row */
+	uint64_t count;         /* surviving rows of the group */
+	uint8_t key[2];         /* the key bytes (str keys: heap offsets) */
+	uint8_t _pad[6];
+} mgdk_gsgroup;
+/* c_0 = s; c_i = BATselect / BATthetaselect(preds[i].b, c_{i-1}, ...) for 0..4
+ * predicates; k_j = BATproject(c, keys[j]) for 1..2 keys; (g, e, h) =
+ * BATgroup(k_0), refined by BATgroup(k_1, g, e, h); per sum BATgroupsum(x, g,
+ * e, NULL, hge, skip_nils = true) with x the product of its 1..3 factors
+ * (BATcalcmul into hge, nested from the left), each factor BATproject(c, b)
+ * or BATcalccstadd / BATcalccstsub(cst:lng, that projection) into lng; the
+ * count is BATgroupcount(k_0, g, e, NULL, lng, skip_nils = false).  Groups
+ * come in BATgroup's order (first occurrence among the survivors): groups[i]
+ * with first = BATproject(e, c)[i]; sumres[i * nsums + j] the hge sum, nil
+ * when nonnil[i * nsums + j] (its non-nil terms) is 0.  The fused entry
+ * computes this in one pass for predicate and operand columns as
+ * mgdk_select_sum_fused takes them, key columns of tail width 1 (bte, or str
+ * with a heap below 64 KiB, whose offsets stand for the strings), at most 8
+ * groups and 6 sums, and returns 0 only when no factor can leave lng and no
+ * order of summation could overflow hge (survivors x the product of the
+ * factors' largest magnitudes < 2^127, from the survivors' minima and
+ * maxima).  Returns 0: done; 1: not applicable (more than maxgroups groups
+ * included), nothing computed and no error set, the caller runs the
+ * operators; -1: error. */
+int mgdk_select_groupsum_fused(const mgdk_selpred *preds, int npreds, mgdk_bat *s,
+			       mgdk_bat *const *keys, int nkeys, const mgdk_gsumexpr *sums, int nsums,
+			       int maxgroups, int *ngroups, mgdk_gsgroup *groups,
+			       void *sumres /* [ngroups][nsums] hge, group-id order */,
+			       uint64_t *nonnil /* [ngroups][nsums] */);
+/* the same request through the operators; never returns 1, more than
+ * maxgroups groups is an error */
+int mgdk_select_groupsum_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s,
+				   mgdk_bat *const *keys, int nkeys, const mgdk_gsumexpr *sums, int nsums,
+				   int maxgroups, int *ngroups, mgdk_gsgroup *groups,
+				   void *sumres, uint64_t *nonnil);
+/* as mgdk_select_sum_last_lines, for the calling thread's last mgdk_select_groupsum_fused */
+unsigned long long mgdk_select_groupsum_last_lines(void);
+/* BATgroupavg3's average (rounded half away from zero) and remainder of one
+ * group from its exact sum (16 bytes, hge) and its count n > 0; -1 when n <= 0 */
+int mgdk_avg3_of_sum(const void *sum_hge, int64_t n, int64_t *avg, int64_t *rem);
+
 /* ---- synthetic TPC-H lineitem generated directly in HBM (same values as
  *      oracle/tpch_gen.c); cols: shipdate(date), quantity, extendedprice,
  *      discount, tax (lng), returnflag, linestatus (str, 1-byte offsets) -- */

@@ -236,9 +236,124 @@ select_sum_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s, const m
 	return 0;
 }
 
+// the grouped fragment (mgdk_select_groupsum_fused) through the operators:
+// the selects, a projection per key and per factor, BATgroup refined by the
+// second key, the constant +- column factors into lng, the products into hge
+// from the left, BATgroupsum per sum (and BATgroupcount of the non-nil terms),
+// BATgroupcount, and the keys and first rows through the extents
+int
+select_groupsum_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s, mgdk_bat *const *keys, int nkeys,
+			  const mgdk_gsumexpr *sums, int nsums, int maxgroups, int *ngroups, mgdk_gsgroup *groups,
+			  void *sumres, uint64_t *nonnil)
+{
+	if (keys == nullptr || nkeys < 1 || nkeys > 2 || keys[0] == nullptr || ngroups == nullptr || npreds < 0 ||
+	    nsums < 0) {
+		seterr("select_groupsum: one or two key columns are required");
+		return -1;
+	}
+	Bats t;
+	mgdk_bat *c = s;
+	for (int i = 0; i < npreds; i++) {
+		const mgdk_selpred &p = preds[i];
+		c = t.add(p.op ? mgdk_BATthetaselect(p.b, c, p.tl, p.op)
+			       : mgdk_BATselect(p.b, c, p.tl, p.th, p.li, p.hi, p.anti, p.nil_matches));
+		if (!c)
+			return -1;
+	}
+	if (c == nullptr) {
+		// no select at all: every row of the keys
+		Cand ci;
+		if (cand_init(&ci, keys[0], nullptr) < 0 || !(c = t.add(cand_slice(ci))))
+			return -1;
+	}
+	mgdk_bat *g = nullptr, *e = nullptr, *h = nullptr, *k[2] = {nullptr, nullptr};
+	for (int j = 0; j < nkeys; j++) {
+		if (keys[j] == nullptr || !(k[j] = t.add(mgdk_BATproject(c, keys[j]))))
+			return -1;
+		mgdk_bat *g2, *e2, *h2;
+		if (mgdk_BATgroup(&g2, &e2, &h2, k[j], nullptr, g, e, h) < 0)
+			return -1;
+		g = t.add(g2), e = t.add(e2), h = t.add(h2);
+	}
+	const BUN ng = e->count;
+	if (ng > (BUN) (maxgroups < 0 ? 0 : maxgroups)) {
+		seterr("select_groupsum: more groups (%llu) than room for results", (unsigned long long) ng);
+		return -1;
+	}
+	std::vector<mgdk_bat *> sv(nsums), nv(nsums);
+	for (int j = 0; j < nsums; j++) {
+		if (sums[j].nf < 1 || sums[j].nf > 3) {
+			seterr("select_groupsum: a sum has one to three factors");
+			return -1;
+		}
+		mgdk_bat *x = nullptr;
+		for (int q = 0; q < sums[j].nf; q++) {
+			const mgdk_gsfactor &f = sums[j].f[q];
+			mgdk_bat *v = f.b ? t.add(mgdk_BATproject(c, f.b)) : nullptr;
+			if (v && f.op == '+')
+				v = t.add(mgdk_BATcalccstadd(&f.cst, MGDK_lng, v, nullptr, MGDK_lng));
+			else if (v && f.op == '-')
+				v = t.add(mgdk_BATcalccstsub(&f.cst, MGDK_lng, v, nullptr, MGDK_lng));
+			else if (v && f.op != 0) {
+				seterr("select_groupsum: a factor is b, cst + b or cst - b");
+				return -1;
+			}
+			if (v && q > 0)
+				v = t.add(mgdk_BATcalcmul(x, v, nullptr, nullptr, MGDK_hge));
+			if (!(x = v))
+				return -1;
+		}
+		sv[j] = t.add(mgdk_BATgroupsum(x, g, e, nullptr, MGDK_hge, true));
+		nv[j] = t.add(mgdk_BATgroupcount(x, g, e, nullptr, MGDK_lng, true));
+		if (!sv[j] || !nv[j])
+			return -1;
+	}
+	mgdk_bat *cn = t.add(mgdk_BATgroupcount(k[0], g, e, nullptr, MGDK_lng, false));
+	mgdk_bat *kf = t.add(mgdk_BATproject(e, c));
+	mgdk_bat *kk[2] = {t.add(mgdk_BATproject(e, k[0])), nkeys > 1 ? t.add(mgdk_BATproject(e, k[1])) : nullptr};
+	if (!cn || !kf || !kk[0] || (nkeys > 1 && !kk[1]))
+		return -1;
+	std::vector<hge> vs((size_t) ng * nsums);
+	std::vector<int64_t> vn((size_t) ng * nsums), vc(ng);
+	std::vector<oid> vf(ng);
+	std::vector<uint8_t> vk[2] = {std::vector<uint8_t>(ng), std::vector<uint8_t>(ng)};
+	Readback rb;
+	for (int j = 0; j < nsums; j++) {
+		rb.add(sv[j], vs.data() + (size_t) j * ng);
+		rb.add(nv[j], vn.data() + (size_t) j * ng);
+	}
+	rb.add(cn, vc.data()), rb.add(kf, vf.data()), rb.add(kk[0], vk[0].data());
+	if (nkeys > 1)
+		rb.add(kk[1], vk[1].data());
+	if (rb.run() < 0)
+		return -1;
+	for (BUN i = 0; i < ng; i++) {
+		mgdk_gsgroup &o = groups[i];
+		memset(&o, 0, sizeof(o));
+		o.first = vf[i];
+		o.count = (uint64_t) vc[i];
+		o.key[0] = vk[0][i];
+		o.key[1] = nkeys > 1 ? vk[1][i] : 0;
+		for (int j = 0; j < nsums; j++) {
+			memcpy((char *) sumres + 16 * ((size_t) i * nsums + j), &vs[(size_t) j * ng + i], 16);
+			nonnil[(size_t) i * nsums + j] = (uint64_t) vn[(size_t) j * ng + i];
+		}
+	}
+	*ngroups = (int) ng;
+	return 0;
+}
+
 }  // namespace mgdk
 
 extern "C" {
+
+int mgdk_select_groupsum_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s, mgdk_bat *const *keys,
+				   int nkeys, const mgdk_gsumexpr *sums, int nsums, int maxgroups, int *ngroups,
+				   mgdk_gsgroup *groups, void *sumres, uint64_t *nonnil)
+{
+	return select_groupsum_opatatime(preds, npreds, s, keys, nkeys, sums, nsums, maxgroups, ngroups, groups, sumres,
+					 nonnil);
+}
 
 int mgdk_select_sum_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s, const mgdk_sumexpr *sums,
 			      int nsums, void *results, uint64_t *count)

@@ -69,6 +69,21 @@ class SumExpr(C.Structure):
     _fields_ = [("a", P), ("b", P)]
 
 
+class GsFactor(C.Structure):
+    """mgdk_gsfactor: b, cst + b or cst - b."""
+    _fields_ = [("b", P), ("op", C.c_char), ("cst", C.c_int64)]
+
+
+class GSumExpr(C.Structure):
+    """mgdk_gsumexpr: the product of f[0 .. nf)."""
+    _fields_ = [("f", GsFactor * 3), ("nf", C.c_int)]
+
+
+class GsGroup(C.Structure):
+    """mgdk_gsgroup: one group of a select_groupsum."""
+    _fields_ = [("first", C.c_uint64), ("count", C.c_uint64), ("key", C.c_uint8 * 2), ("_pad", C.c_uint8 * 6)]
+
+
 class GDKError(RuntimeError):
     pass
 
@@ -248,6 +263,14 @@ _SIGS = {
     "mgdk_select_sum_opatatime": (C.c_int, [C.POINTER(SelPred), C.c_int, P, C.POINTER(SumExpr), C.c_int,
                                             C.c_void_p, C.POINTER(C.c_uint64)]),
     "mgdk_select_sum_last_lines": (C.c_ulonglong, []),
+    "mgdk_select_groupsum_fused": (C.c_int, [C.POINTER(SelPred), C.c_int, P, C.POINTER(P), C.c_int,
+                                             C.POINTER(GSumExpr), C.c_int, C.c_int, C.POINTER(C.c_int),
+                                             C.POINTER(GsGroup), C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mgdk_select_groupsum_opatatime": (C.c_int, [C.POINTER(SelPred), C.c_int, P, C.POINTER(P), C.c_int,
+                                                 C.POINTER(GSumExpr), C.c_int, C.c_int, C.POINTER(C.c_int),
+                                                 C.POINTER(GsGroup), C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mgdk_select_groupsum_last_lines": (C.c_ulonglong, []),
+    "mgdk_avg3_of_sum": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mgdk_tpch_lineitem": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, PP]),
     "mgdk_gen_window_column": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, PP, PP]),
     "mgdk_BAThashpartition": (C.c_int, [PP, C.c_void_p, C.c_int, C.c_void_p]),
@@ -1391,6 +1414,23 @@ def q6_opatatime(shipdate, discount, quantity, price, d0, d1, dlo, dhi, qmax):
     return hge_to_int(out)
 
 
+def _selpreds(preds, keep):
+    """The mgdk_selpred array of a select cascade (see select_sum)."""
+    cp = (SelPred * max(1, len(preds)))()
+    for i, p in enumerate(preds):
+        b = p[0]
+        cp[i].b = b.ptr
+        if len(p) == 3:
+            cp[i].tl = _valptr(b.ttype, p[1], keep)
+            cp[i].op = p[2].encode()
+        else:
+            cp[i].tl = _valptr(b.ttype, p[1], keep)
+            cp[i].th = _valptr(b.ttype, p[2], keep)
+            cp[i].li, cp[i].hi, cp[i].anti = bool(p[3]), bool(p[4]), bool(p[5])
+            cp[i].nil_matches = bool(p[6]) if len(p) > 6 else False
+    return cp
+
+
 def select_sum(preds, sums, s=None, fused=True, fallback=True):
     """A select cascade and exact sums over its survivors (mgdk_select_sum_fused).
 
@@ -1404,18 +1444,7 @@ def select_sum(preds, sums, s=None, fused=True, fallback=True):
     nothing was computed.  fused=False runs the operators."""
     keep = []
     npr, ns = len(preds), len(sums)
-    cp = (SelPred * max(1, npr))()
-    for i, p in enumerate(preds):
-        b = p[0]
-        cp[i].b = b.ptr
-        if len(p) == 3:
-            cp[i].tl = _valptr(b.ttype, p[1], keep)
-            cp[i].op = p[2].encode()
-        else:
-            cp[i].tl = _valptr(b.ttype, p[1], keep)
-            cp[i].th = _valptr(b.ttype, p[2], keep)
-            cp[i].li, cp[i].hi, cp[i].anti = bool(p[3]), bool(p[4]), bool(p[5])
-            cp[i].nil_matches = bool(p[6]) if len(p) > 6 else False
+    cp = _selpreds(preds, keep)
     cs = (SumExpr * max(1, ns))()
     for j, e in enumerate(sums):
         a, b = e if isinstance(e, (tuple, list)) else (e, None)
@@ -1443,6 +1472,80 @@ def select_sum_last_lines():
     """128-B lines the last fused select_sum on this thread read of every
     column but the first predicate's (which is read whole)."""
     return int(lib().mgdk_select_sum_last_lines())
+
+
+def select_groupsum(preds, keys, sums, s=None, fused=True, fallback=True, maxgroups=64):
+    """A select cascade, GROUP BY one or two one-byte key columns, exact hge
+    sums and counts over the survivors (mgdk_select_groupsum_fused).
+
+    preds: as select_sum takes them (none at all: every row, or every
+    candidate of s); keys: one or two BATs (bte, or str with one-byte
+    offsets); sums: each a BAT, or a tuple of one to three factors, a factor
+    being a BAT, ("+", cst, BAT) for cst + BAT or ("-", cst, BAT) for
+    cst - BAT as lng, the product taken as hge from the left.  Returns
+    (groups, used_fused): groups in BATgroup's order (first occurrence among
+    the survivors), each a dict with `first` (oid of the group's first
+    surviving row), `keys` (the key bytes), `count`, `sums` (int, or None for
+    nil) and `nonnil` (non-nil terms per sum).  fused=True tries the one-pass
+    kernel; when it is not applicable (more than 8 groups, a factor or a sum
+    that could overflow, ...) the operators run instead (used_fused False) --
+    or, with fallback=False, None is returned and nothing was computed.
+    fused=False runs the operators."""
+    keep = []
+    npr, nk, ns = len(preds), len(keys), len(sums)
+    cp = _selpreds(preds, keep)
+    ck = (P * max(1, nk))(*[k.ptr for k in keys])
+    cs = (GSumExpr * max(1, ns))()
+    for j, e in enumerate(sums):
+        fs = e if isinstance(e, (tuple, list)) else (e,)
+        if not 1 <= len(fs) <= 3:
+            raise ValueError("select_groupsum: a sum has one to three factors")
+        cs[j].nf = len(fs)
+        for q, f in enumerate(fs):
+            if isinstance(f, (tuple, list)):
+                op, cst, b = f
+                cs[j].f[q].op = op.encode()
+                cs[j].f[q].cst = cst
+            else:
+                b = f
+            cs[j].f[q].b = b.ptr
+    ng = C.c_int()
+    grp = (GsGroup * max(1, maxgroups))()
+    res = (C.c_uint64 * (2 * max(1, maxgroups * ns)))()
+    nn = (C.c_uint64 * max(1, maxgroups * ns))()
+    args = (cp, npr, _p(s), ck, nk, cs, ns, maxgroups, C.byref(ng), grp, C.cast(res, C.c_void_p), nn)
+    used = False
+    if fused:
+        rc = lib().mgdk_select_groupsum_fused(*args)
+        if rc < 0:
+            raise _err()
+        used = rc == 0
+        if not used and not fallback:
+            return None
+    if not used:
+        _chk(lib().mgdk_select_groupsum_opatatime(*args))
+    out = []
+    for i in range(ng.value):
+        vals = [hge_to_int(res[2 * (i * ns + j):2 * (i * ns + j) + 2]) for j in range(ns)]
+        out.append(dict(first=int(grp[i].first), keys=tuple(int(grp[i].key[k]) for k in range(nk)),
+                        count=int(grp[i].count), sums=[None if v == NIL[TYPE_hge] else v for v in vals],
+                        nonnil=[int(nn[i * ns + j]) for j in range(ns)]))
+    return out, used
+
+
+def select_groupsum_last_lines():
+    """128-B lines the last fused select_groupsum on this thread read of every
+    column but the first predicate's (which is read whole)."""
+    return int(lib().mgdk_select_groupsum_last_lines())
+
+
+def avg3_of_sum(total, n):
+    """BATgroupavg3's (average rounded half away from zero, remainder) of one
+    group from its exact sum and its count n > 0."""
+    buf = (C.c_uint64 * 2)(*int_to_hge_words(int(total)))
+    avg, rem = C.c_int64(), C.c_int64()
+    _chk(lib().mgdk_avg3_of_sum(C.cast(buf, C.c_void_p), int(n), C.byref(avg), C.byref(rem)))
+    return int(avg.value), int(rem.value)
 
 
 def q1_fused(cols, dmax, maxgroups=64, fused=True):

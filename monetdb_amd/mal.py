@@ -66,6 +66,7 @@ def ALGthetaselect2(gdk, b, s, val, op):
 # type, as in `batcalc.*(pa, pb):hge`.
 
 SELECTS = ("algebra.select", "algebra.thetaselect")
+FUSED = ("mgdk.select_sum", "mgdk.select_groupsum")
 
 
 def _ttype(b):
@@ -121,6 +122,34 @@ def _run_one(gdk, ins, env):
         out = gdk.BATthetaselect(b, s, *call) if name == "algebra.thetaselect" else gdk.BATselect(b, s, *call)
     elif name == "algebra.projection":
         out = gdk.BATproject(val(args[0]), val(args[1]))
+    elif name in ("group.group", "group.subgroup"):
+        b = val(args[0])
+        g = val(args[1]) if name == "group.subgroup" else None
+        out = gdk.BATgroup(b, None, g)
+        for r, o in zip(res, out):
+            env[r] = o
+        return
+    elif name in ("batcalc.+", "batcalc.-") and tp == "lng" and not isvar(args[0]):
+        # cst + b / cst - b: the constant is an lng (BATcalccstadd / BATcalccstsub)
+        cst, b = args[0], val(args[1])
+        if hasattr(gdk, "BATcalc"):
+            out = gdk.BATcalc(name[8:], None, b, gdk.TYPE_lng, c1=cst, t1=gdk.TYPE_lng)
+        else:
+            out = (gdk.BATcalccstadd if name[8:] == "+" else gdk.BATcalccstsub)(cst, gdk.TYPE_lng, b, gdk.TYPE_lng)
+    elif name == "aggr.subsum":
+        if tp != "hge":
+            raise ValueError(f"{fn}: only an hge result is executed here")
+        out = gdk.BATgroupsum(val(args[0]), val(args[1]), val(args[2]), gdk.TYPE_hge, True)
+    elif name == "aggr.subcount":
+        out = gdk.BATgroupcount(val(args[0]), val(args[1]), val(args[2]), False)
+    elif name == "aggr.subavg":
+        out = gdk.BATgroupavg3(val(args[0]), val(args[1]), val(args[2]), True)
+        for r, o in zip(res, out):
+            env[r] = o
+        return
+    elif name == "mgdk.select_groupsum":
+        _run_select_groupsum(gdk, ins, env)
+        return
     elif name.startswith("batcalc.") and name[8:] in ("*", "+", "-"):
         if tp != "hge":
             raise ValueError(f"{fn}: only an hge result is executed here")
@@ -168,13 +197,16 @@ def run_plan(gdk, plan, env=None, fuse=True):
     """Execute a plan against a GDK binding (monetdb_amd.gdk or the
     oracle's Python module); returns the variables, `env` included.  Executed:
     algebra.select / thetaselect / projection, batcalc.* / + / - into hge,
-    aggr.sum into hge, aggr.count and the mgdk.select_sum that
-    fuse_select_sum puts in.  fuse=True (the default: the fused operator beat
-    the operators where it was measured) applies that rewrite
-    first; a plan that is already rewritten is left as it is."""
+    aggr.sum into hge, aggr.count, group.group / subgroup, batcalc.+ / - of a
+    constant and a BAT into lng, aggr.subsum into hge, aggr.subcount,
+    aggr.subavg (three results) and the mgdk.select_sum / mgdk.select_groupsum
+    that fuse_select_sum / fuse_select_groupsum put in.  fuse=True (the
+    default: the fused operators beat the operators where they were measured,
+    DESIGN.md 11.10, 11.11) applies those rewrites first; a plan that is
+    already rewritten is left as it is."""
     env = dict(env or {})
     if fuse:
-        plan = fuse_select_sum(plan)
+        plan = fuse_select_groupsum(fuse_select_sum(plan))
     for ins in plan:
         _run_one(gdk, ins, env)
     return env
@@ -201,7 +233,7 @@ def fuse_select_sum(plan):
         for r in res:
             defs[r] = i
     for i, (res, fn, args) in enumerate(plan):
-        if _split(fn)[0] == "mgdk.select_sum":
+        if _split(fn)[0] in FUSED:
             continue
         for a in args:
             if isinstance(a, str) and a in defs and defs[a] < i:
@@ -282,3 +314,267 @@ def fuse_select_sum(plan):
         elif i not in taken:
             out.append(ins)
     return out
+
+
+# ---- the grouped fragment ------------------------------------------------------
+
+GS_MAXKEYS, GS_MAXSUMS, GS_MAXFACTORS = 2, 6, 3
+
+
+def _run_select_groupsum(gdk, ins, env):
+    """mgdk.select_groupsum: the fused operator where the binding has one and
+    it applies -- its group results then stand in for the aggr.sub* results and
+    for the projections through the extents -- otherwise the instructions the
+    rewrite replaced."""
+    res, _, (spec,) = ins
+    r = None
+    if hasattr(gdk, "select_groupsum"):
+        preds = []
+        for fn, col, rest in spec["preds"]:
+            b = env[col]
+            preds.append((b,) + tuple(_pred_call(gdk, b, fn, rest)))
+        keys = [env[k] for k in spec["keys"]]
+        sums = [tuple(env[f] if isinstance(f, str) else (f[0], f[1], env[f[2]]) for f in fs)
+                for fs in spec["sums"]]
+        s = env[spec["s"]] if spec["s"] is not None else None
+        r = gdk.select_groupsum(preds, keys, sums, s, fused=True, fallback=False)
+    if r is None:
+        for k in spec["kept"]:
+            _run_one(gdk, k, env)
+        return
+    groups, _ = r
+    lng = (lambda vals: gdk.BAT.from_numpy(gdk.TYPE_lng, [gdk.NIL[gdk.TYPE_lng] if v is None else v for v in vals]))
+    first = gdk.BAT.from_numpy(gdk.TYPE_oid, [g["first"] for g in groups])
+    for out in spec["outs"]:
+        kind = out[0]
+        if kind == "sum":
+            words = [gdk.int_to_hge_words(gdk.NIL[gdk.TYPE_hge] if g["sums"][out[2]] is None else g["sums"][out[2]])
+                     for g in groups]
+            env[out[1]] = gdk.BAT.from_numpy(gdk.TYPE_hge, [w for lohi in words for w in lohi])
+        elif kind == "count":
+            env[out[1]] = lng([g["count"] for g in groups])
+        elif kind == "avg":
+            # BATgroupavg3 of the column from its exact sum: a group without
+            # a non-nil value has a nil average, remainder 0 and count 0
+            (a, rm, n), j, col = out[1], out[2], out[3]
+            tp = _ttype(env[col])
+            trip = [gdk.avg3_of_sum(g["sums"][j], g["nonnil"][j]) if g["nonnil"][j] else (gdk.NIL[tp], 0)
+                    for g in groups]
+            env[a] = gdk.BAT.from_numpy(tp, [t[0] for t in trip])
+            env[rm] = lng([t[1] for t in trip])
+            env[n] = lng([g["nonnil"][j] for g in groups])
+        elif kind == "first":
+            env[out[1]] = first
+        else:                           # "proj": a column at the groups' first rows
+            env[out[1]] = gdk.BATproject(first, env[out[2]])
+
+
+def fuse_select_groupsum(plan):
+    """Replace every fragment
+
+        c1 := algebra.select | algebra.thetaselect(col1 [, s], ...) ... c_k     up to four, or none (c_k = s)
+        p  := algebra.projection(ck, col)                                        keys and operands
+        (g1, e1, h1) := group.group(pk0);  (g, e, h) := group.subgroup(pk1, g1)  the second one optional
+        f  := batcalc.+(cst, p):lng | batcalc.-(cst, p):lng                      a factor (or p itself)
+        m  := batcalc.*(f | m, f):hge                                            products, nested from the left
+        r  := aggr.subsum(p | f | m, g, e):hge                                   up to six sums in all
+        n  := aggr.subcount(p, g, e)
+        (a, r, n) := aggr.subavg(p, g, e)                                        over a projected column only
+        k  := algebra.projection(e, p | ck)                                      keys / first rows of the groups
+
+    by one instruction (results, "mgdk.select_groupsum", (spec,)) placed
+    where the fragment's last instruction stood; spec holds the predicates,
+    the key and operand columns, what each result is ("outs") and, under
+    "kept", the instructions it replaces.  Nothing is rewritten unless every
+    candidate list, projection, factor, product, group-id BAT and histogram is
+    used inside the fragment only and the final extents feed nothing but the
+    aggregates and such projections."""
+    plan = list(plan)
+    defs, uses = {}, {}
+    for i, (res, fn, args) in enumerate(plan):
+        for r in res:
+            defs[r] = i
+    for i, (res, fn, args) in enumerate(plan):
+        if _split(fn)[0] in FUSED:
+            continue
+        for a in args:
+            if isinstance(a, str) and a in defs and defs[a] < i:
+                uses.setdefault(a, []).append(i)
+    name_of = (lambda i: _split(plan[i][1])[0])
+    type_of = (lambda i: _split(plan[i][1])[1])
+    isdef = (lambda a: isinstance(a, str) and a in defs)
+    replaced, taken = {}, set()
+    for i0 in range(len(plan)):
+        if name_of(i0) != "group.group" or len(plan[i0][0]) != 3 or len(plan[i0][2]) != 1:
+            continue
+        spec_idx = _groupsum_fragment(plan, i0, defs, uses, name_of, type_of, isdef)
+        if spec_idx is None:
+            continue
+        res, spec, idx = spec_idx
+        if idx & taken:
+            continue
+        spec["kept"] = [plan[i] for i in sorted(idx)]
+        taken |= idx
+        replaced[max(idx)] = (res, "mgdk.select_groupsum", (spec,))
+    out = []
+    for i, ins in enumerate(plan):
+        if i in replaced:
+            out.append(replaced[i])
+        elif i not in taken:
+            out.append(ins)
+    return out
+
+
+def _groupsum_fragment(plan, i0, defs, uses, name_of, type_of, isdef):
+    """(results, spec without "kept", instruction indices) of the fragment
+    around the group.group at i0, or None."""
+    idx = {i0}
+    keyvars = [plan[i0][2][0]]
+    g, e, h = plan[i0][0]
+    # the refining subgroup: the only user of g1, with e1 and h1 unused
+    sub = [u for u in uses.get(g, []) if name_of(u) == "group.subgroup"]
+    if sub:
+        u = sub[0]
+        if uses.get(g) != [u] or uses.get(e) or uses.get(h) or len(plan[u][2]) != 2 or plan[u][2][1] != g \
+                or len(plan[u][0]) != 3:
+            return None
+        idx.add(u)
+        keyvars.append(plan[u][2][0])
+        g, e, h = plan[u][0]
+        if any(name_of(v) == "group.subgroup" for v in uses.get(g, [])):
+            return None                  # three keys
+    if uses.get(h):
+        return None
+    # the keys: projections of one candidate list
+    if not all(isdef(k) and name_of(defs[k]) == "algebra.projection" for k in keyvars):
+        return None
+    ck = plan[defs[keyvars[0]]][2][0]
+    if not isinstance(ck, str):
+        return None
+    # a fragment projection: algebra.projection(ck, column), the column a plan input
+    def proj_col(v):
+        if not isdef(v) or name_of(defs[v]) != "algebra.projection":
+            return None
+        l, r = plan[defs[v]][2][:2]
+        return r if l == ck and isinstance(r, str) and not isdef(r) else None
+
+    def factor(v):
+        """col, (op, cst, col), or None"""
+        c = proj_col(v)
+        if c is not None:
+            idx.add(defs[v])
+            return c
+        if not isdef(v):
+            return None
+        d = defs[v]
+        if name_of(d) in ("batcalc.+", "batcalc.-") and type_of(d) == "lng" and len(plan[d][2]) == 2:
+            cst, p = plan[d][2]
+            if isinstance(cst, int) and not isinstance(cst, bool) and proj_col(p) is not None:
+                idx.update((d, defs[p]))
+                return (name_of(d)[8:], cst, proj_col(p))
+        return None
+
+    def factors(v):
+        f = factor(v)
+        if f is not None:
+            return [f]
+        if not isdef(v):
+            return None
+        d = defs[v]
+        if name_of(d) == "batcalc.*" and type_of(d) == "hge" and len(plan[d][2]) == 2:
+            left, right = factors(plan[d][2][0]), factor(plan[d][2][1])
+            if left is None or right is None:
+                return None
+            idx.add(d)
+            return left + [right]
+        return None
+
+    keys = [proj_col(k) for k in keyvars]
+    if None in keys:
+        return None
+    idx.update(defs[k] for k in keyvars)
+    sums, outs, res = [], [], []
+    aggrs = sorted(set(uses.get(g, [])))
+    for u in aggrs:
+        nm, args = name_of(u), plan[u][2]
+        if len(args) != 3 or args[1] != g or args[2] != e:
+            return None
+        if nm == "aggr.subsum" and type_of(u) == "hge" and len(plan[u][0]) == 1:
+            fs = factors(args[0])
+            if fs is None or len(fs) > GS_MAXFACTORS:
+                return None
+            fs = tuple(fs)
+            if fs not in sums:
+                sums.append(fs)
+            outs.append(("sum", plan[u][0][0], sums.index(fs)))
+        elif nm == "aggr.subcount" and len(plan[u][0]) == 1:
+            if proj_col(args[0]) is None:
+                return None
+            idx.add(defs[args[0]])
+            outs.append(("count", plan[u][0][0]))
+        elif nm == "aggr.subavg" and len(plan[u][0]) == 3:
+            c = proj_col(args[0])
+            if c is None:
+                return None
+            idx.add(defs[args[0]])
+            if (c,) not in sums:
+                sums.append((c,))
+            outs.append(("avg", tuple(plan[u][0]), sums.index((c,)), c))
+        else:
+            return None
+        idx.add(u)
+        res.extend(plan[u][0])
+    if not aggrs or len(sums) > GS_MAXSUMS:
+        return None
+    # the extents: the aggregates, and projections of the fragment's own columns
+    for u in sorted(set(uses.get(e, []))):
+        if u in idx:
+            continue
+        if name_of(u) != "algebra.projection" or plan[u][2][0] != e or len(plan[u][0]) != 1:
+            return None
+        x = plan[u][2][1]
+        if x == ck:
+            outs.append(("first", plan[u][0][0]))
+        elif proj_col(x) is not None:
+            idx.add(defs[x])
+            outs.append(("proj", plan[u][0][0], proj_col(x)))
+        else:
+            return None
+        idx.add(u)
+        res.append(plan[u][0][0])
+    # the select chain behind ck: every link used by the fragment only
+    chain, s = [], None
+    if isdef(ck):
+        c = ck
+        while True:
+            i = defs[c]
+            if name_of(i) not in SELECTS or len(plan[i][0]) != 1:
+                return None
+            col, cand, rest = _select_split(name_of(i), plan[i][2])
+            chain.append(i)
+            if cand is None:
+                break
+            if not isdef(cand) or defs[cand] > i:
+                s = cand                 # a plan input: the first candidate list
+                break
+            if uses.get(cand, []) != [i]:
+                return None
+            c = cand
+        chain.reverse()
+        if len(chain) > 4:
+            return None
+        idx.update(chain)
+    else:
+        s = ck                           # no select: the groups of a plan's candidate list
+    # nothing of the fragment but its results may be used outside it
+    inner = set()
+    for i in idx:
+        inner.update(plan[i][0])
+    for v in inner - set(res):
+        if any(u not in idx for u in uses.get(v, [])):
+            return None
+    spec = {"s": s, "preds": [], "keys": keys, "sums": sums, "outs": outs}
+    for i in chain:
+        col, cand, rest = _select_split(name_of(i), plan[i][2])
+        spec["preds"].append((name_of(i), col, rest))
+    return tuple(res), spec, idx
