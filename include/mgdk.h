@@ -605,13 +605,44 @@ int mgdk_select_groupsum_fused(const mgdk_selpred *preds, int npreds, mgdk_bat *
 			       void *sumres /* [ngroups][nsums] hge, group-id order */,
 			       uint64_t *nonnil /* [ngroups][nsums] */);
 /* the same request through the operators; never returns 1, more than
- * maxgroups groups is an error */
+ * maxgroups groups is an error, and so is a key column wider than the one
+ * byte that mgdk_gsgroup holds */
 int mgdk_select_groupsum_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s,
 				   mgdk_bat *const *keys, int nkeys, const mgdk_gsumexpr *sums, int nsums,
 				   int maxgroups, int *ngroups, mgdk_gsgroup *groups,
 				   void *sumres, uint64_t *nonnil);
 /* as mgdk_select_sum_last_lines, for the calling thread's last mgdk_select_groupsum_fused */
 unsigned long long mgdk_select_groupsum_last_lines(void);
+/* ---- the same fragment for wider keys and more groups: 1..2 key columns,
+ *      each a column as the predicates take them (bte, sht, int, lng, date,
+ *      daytime, timestamp) or a str column with offsets of 1 or 2 bytes and a
+ *      heap below 64 KiB, their widths together at most 8 bytes, and at most
+ *      256 groups.  A nil key is a key like any other.  Everything else --
+ *      predicates, sums, candidate lists, the order of the groups, the
+ *      overflow rule, the return values -- is mgdk_select_groupsum_fused's;
+ *      keys of more than 8 bytes together, a 257th group or maxgroups <
+ *      ngroups answer 1 -------------------------------- */
+typedef struct mgdk_gsgroupw {
+	mgdk_oid first;         /* oid of the group's first surviving row */
+	uint64_t count;         /* surviving rows of the group */
+	int64_t key[2];         /* the key's tail value sign-extended; str keys: the heap offset zero-extended */
+} mgdk_gsgroupw;
+int mgdk_select_groupsum_hash_fused(const mgdk_selpred *preds, int npreds, mgdk_bat *s,
+				    mgdk_bat *const *keys, int nkeys, const mgdk_gsumexpr *sums, int nsums,
+				    int maxgroups, int *ngroups, mgdk_gsgroupw *groups,
+				    void *sumres /* [ngroups][nsums] hge, group-id order */,
+				    uint64_t *nonnil /* [ngroups][nsums] */);
+/* the same request through the operators, the keys read back at their own
+ * width (the raw tail bits, for a type that is no integer); never returns 1;
+ * more than maxgroups groups, or a key column that is not 1, 2, 4 or 8 bytes
+ * wide, is an error */
+int mgdk_select_groupsum_hash_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s,
+					mgdk_bat *const *keys, int nkeys, const mgdk_gsumexpr *sums, int nsums,
+					int maxgroups, int *ngroups, mgdk_gsgroupw *groups,
+					void *sumres, uint64_t *nonnil);
+/* as mgdk_select_groupsum_last_lines, for the calling thread's last
+ * mgdk_select_groupsum_hash_fused; a key column of width w counts as any column of that width */
+unsigned long long mgdk_select_groupsum_hash_last_lines(void);
 /* BATgroupavg3's average (rounded half away from zero) and remainder of one
  * group from its exact sum (16 bytes, hge) and its count n > 0; -1 when n <= 0 */
 int mgdk_avg3_of_sum(const void *sum_hge, int64_t n, int64_t *avg, int64_t *rem);

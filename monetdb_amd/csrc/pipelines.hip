@@ -240,12 +240,17 @@ select_sum_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s, const m
 // the selects, a projection per key and per factor, BATgroup refined by the
 // second key, the constant +- column factors into lng, the products into hge
 // from the left, BATgroupsum per sum (and BATgroupcount of the non-nil terms),
-// BATgroupcount, and the keys and first rows through the extents
+// BATgroupcount, and the keys and first rows through the extents.  G is
+// mgdk_gsgroup (the keys' bytes) or mgdk_gsgroupw (the hashed entry's twin:
+// the keys read back at their own width, sign-extended, str offsets
+// zero-extended)
+template <typename G>
 int
 select_groupsum_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s, mgdk_bat *const *keys, int nkeys,
-			  const mgdk_gsumexpr *sums, int nsums, int maxgroups, int *ngroups, mgdk_gsgroup *groups,
+			  const mgdk_gsumexpr *sums, int nsums, int maxgroups, int *ngroups, G *groups,
 			  void *sumres, uint64_t *nonnil)
 {
+	constexpr bool WIDE = sizeof(((G *) nullptr)->key[0]) == 8;
 	if (keys == nullptr || nkeys < 1 || nkeys > 2 || keys[0] == nullptr || ngroups == nullptr || npreds < 0 ||
 	    nsums < 0) {
 		seterr("select_groupsum: one or two key columns are required");
@@ -268,8 +273,21 @@ select_groupsum_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s, mg
 	}
 	mgdk_bat *g = nullptr, *e = nullptr, *h = nullptr, *k[2] = {nullptr, nullptr};
 	for (int j = 0; j < nkeys; j++) {
-		if (keys[j] == nullptr || !(k[j] = t.add(mgdk_BATproject(c, keys[j]))))
+		if (keys[j] == nullptr)
 			return -1;
+		// the group struct holds a key of one byte (of 1, 2, 4 or 8 bytes
+		// for mgdk_gsgroupw): nothing wider, and no void key, is read back
+		auto fits = [](int kw) { return WIDE ? (kw == 1 || kw == 2 || kw == 4 || kw == 8) : kw == 1; };
+		if (!fits(keys[j]->twidth)) {
+			seterr("select_groupsum: a key column of width %d does not fit the result's keys", (int) keys[j]->twidth);
+			return -1;
+		}
+		if (!(k[j] = t.add(mgdk_BATproject(c, keys[j]))))
+			return -1;
+		if (k[j]->count != 0 && !fits(k[j]->twidth)) {
+			seterr("select_groupsum: a key column of width %d does not fit the result's keys", (int) k[j]->twidth);
+			return -1;
+		}
 		mgdk_bat *g2, *e2, *h2;
 		if (mgdk_BATgroup(&g2, &e2, &h2, k[j], nullptr, g, e, h) < 0)
 			return -1;
@@ -316,7 +334,7 @@ select_groupsum_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s, mg
 	std::vector<hge> vs((size_t) ng * nsums);
 	std::vector<int64_t> vn((size_t) ng * nsums), vc(ng);
 	std::vector<oid> vf(ng);
-	std::vector<uint8_t> vk[2] = {std::vector<uint8_t>(ng), std::vector<uint8_t>(ng)};
+	std::vector<uint8_t> vk[2] = {std::vector<uint8_t>(WIDE ? ng * 8 : ng), std::vector<uint8_t>(WIDE ? ng * 8 : ng)};
 	Readback rb;
 	for (int j = 0; j < nsums; j++) {
 		rb.add(sv[j], vs.data() + (size_t) j * ng);
@@ -328,12 +346,22 @@ select_groupsum_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s, mg
 	if (rb.run() < 0)
 		return -1;
 	for (BUN i = 0; i < ng; i++) {
-		mgdk_gsgroup &o = groups[i];
+		G &o = groups[i];
 		memset(&o, 0, sizeof(o));
 		o.first = vf[i];
 		o.count = (uint64_t) vc[i];
-		o.key[0] = vk[0][i];
-		o.key[1] = nkeys > 1 ? vk[1][i] : 0;
+		if constexpr (WIDE) {
+			for (int j = 0; j < nkeys; j++) {
+				const int w = kk[j]->twidth;
+				uint64_t v = 0;
+				memcpy(&v, vk[j].data() + (size_t) i * w, w);
+				const int sh = 64 - 8 * w;
+				o.key[j] = kk[j]->ttype == MGDK_str ? (int64_t) v : (int64_t) (v << sh) >> sh;
+			}
+		} else {
+			o.key[0] = vk[0][i];
+			o.key[1] = nkeys > 1 ? vk[1][i] : 0;
+		}
 		for (int j = 0; j < nsums; j++) {
 			memcpy((char *) sumres + 16 * ((size_t) i * nsums + j), &vs[(size_t) j * ng + i], 16);
 			nonnil[(size_t) i * nsums + j] = (uint64_t) vn[(size_t) j * ng + i];
@@ -350,6 +378,14 @@ extern "C" {
 int mgdk_select_groupsum_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s, mgdk_bat *const *keys,
 				   int nkeys, const mgdk_gsumexpr *sums, int nsums, int maxgroups, int *ngroups,
 				   mgdk_gsgroup *groups, void *sumres, uint64_t *nonnil)
+{
+	return select_groupsum_opatatime(preds, npreds, s, keys, nkeys, sums, nsums, maxgroups, ngroups, groups, sumres,
+					 nonnil);
+}
+
+int mgdk_select_groupsum_hash_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s, mgdk_bat *const *keys,
+					int nkeys, const mgdk_gsumexpr *sums, int nsums, int maxgroups, int *ngroups,
+					mgdk_gsgroupw *groups, void *sumres, uint64_t *nonnil)
 {
 	return select_groupsum_opatatime(preds, npreds, s, keys, nkeys, sums, nsums, maxgroups, ngroups, groups, sumres,
 					 nonnil);

@@ -29,14 +29,13 @@
 // A workgroup writes one table (GsPart); k_gs_fin merges the tables by code
 // through the same LDS structure, orders the groups by first row -- BATgroup's
 // numbering -- and writes one block that the host copies back with one wait.
-#include "selectsum.h"
+#include "selectgroupsum.h"
 
 using namespace mgdk;
 
 namespace {
 
-constexpr int GS_MAXK = 2, GS_MAXG = 8, GS_MAXS = 6, GS_MAXF = 3;
-constexpr int GS_MAXT = GS_MAXS * GS_MAXF;   // columns whose minimum / maximum can be wanted
+constexpr int GS_MAXG = 8;
 constexpr int GS_CELLS = GS_MAXG * GS_MAXS;
 constexpr int GS_REP = 8;                    // replicas of a sum cell
 constexpr uint32_t GS_EMPTY = 0xffffffffu;   // no key code has more than 16 bits
@@ -47,17 +46,6 @@ constexpr uint32_t GS_EMPTY = 0xffffffffu;   // no key code has more than 16 bit
 #define MGDK_GS_BPC 8
 #endif
 
-struct GsF {
-	const char *col;          // the column at the first row of the range
-	int w, op;                // op 0: col; '+': cst + col; '-': cst - col
-	int count;                // first use of the column: its lines are counted here
-	int track;                // 1 + its minimum / maximum slot, at the column's first use; else 0
-	int64_t nil, cst;
-};
-struct GsS {
-	GsF f[GS_MAXF];
-	int nf, pad;
-};
 struct GsK {
 	const char *col;
 	int count, pad;
@@ -119,17 +107,6 @@ gs_slot_claim(uint32_t *codes, uint32_t code)
 			return g;
 	}
 	return -1;
-}
-
-// cell += (hi, lo) modulo 2^128: a returning add on the low word tells this
-// lane the carry its own add produced, whatever else was added meanwhile
-__device__ __forceinline__ void
-gs_add128(unsigned long long *lo, unsigned long long *hi, unsigned long long tlo, unsigned long long thi)
-{
-	const unsigned long long old = atomicAdd(lo, tlo);
-	thi += old + tlo < old;
-	if (thi)
-		atomicAdd(hi, thi);
 }
 
 // replicas of a cell added up
@@ -496,12 +473,6 @@ gs_key(const mgdk_bat *b)
 	return b->ttype == MGDK_str && b->tvheap != nullptr && b->tvheapsize < ((uint64_t) 1 << 16);
 }
 
-inline uhge
-gs_mag(hge v)
-{
-	return v < 0 ? (uhge) 0 - (uhge) v : (uhge) v;
-}
-
 }  // namespace
 
 extern "C" {
@@ -525,16 +496,8 @@ mgdk_select_groupsum_fused(const mgdk_selpred *preds, int npreds, mgdk_bat *s, m
 	for (int j = 0; j < nkeys; j++)
 		if (!gs_key(keys[j]) || !same(keys[j]))
 			return 1;
-	for (int j = 0; j < nsums; j++) {
-		if (sums[j].nf < 1 || sums[j].nf > GS_MAXF)
-			return 1;
-		for (int q = 0; q < sums[j].nf; q++) {
-			const mgdk_gsfactor &f = sums[j].f[q];
-			if (!ss_column(f.b) || !same(f.b) || (f.op != 0 && f.op != '+' && f.op != '-') ||
-			    (f.op != 0 && f.cst == INT64_MIN))
-				return 1;
-		}
-	}
+	if (!gs_sums_ok(sums, nsums, same))
+		return 1;
 	if (s && (s->ttype != MGDK_void || is_complex_cand(s) || s->tseqbase == MGDK_OID_NIL))
 		return 1;
 	// the predicates, normalised: an argument the operators reject leaves
@@ -586,49 +549,10 @@ mgdk_select_groupsum_fused(const mgdk_selpred *preds, int npreds, mgdk_bat *s, m
 		a.k[j].count = first_use(keys[j]);
 		al = al && aligned16(a.k[j].col);
 	}
-	// a column's values lie within its type's width: where that bounds every
-	// factor within lng and rows x the product of the factors' magnitudes
-	// below 2^127, the sum needs no minima and maxima
-	constexpr uhge lim = ((uhge) 1 << 127) - 1, lng_max = (uhge) INT64_MAX;
-	auto sat_mul = [](uhge x, uhge y) { return (x != 0 && y > lim / x) ? lim + 1 : x * y; };
-	const void *tcol[GS_MAXT];
-	int tw[GS_MAXT];
-	for (int j = 0; j < nsums; j++) {
-		GsS &x = a.s[j];
-		x.nf = sums[j].nf;
-		uhge bound = a.n;
-		bool want = false;
-		for (int q = 0; q < x.nf; q++) {
-			const mgdk_gsfactor &f = sums[j].f[q];
-			const uhge mw = ((uhge) 1 << (8 * f.b->twidth - 1)) - 1;
-			const uhge mf = f.op ? gs_mag((hge) f.cst) + mw : mw;
-			if (mf > lng_max)
-				want = true;
-			bound = sat_mul(bound, mf);
-		}
-		want = want || bound > lim;
-		for (int q = 0; q < x.nf; q++) {
-			const mgdk_gsfactor &f = sums[j].f[q];
-			GsF &o = x.f[q];
-			o.w = f.b->twidth;
-			o.col = (const char *) f.b->theap + first * (uint64_t) o.w;
-			o.op = f.op;
-			o.cst = f.cst;
-			o.nil = ss_nil(o.w);
-			o.count = first_use(f.b);
-			al = al && aligned16(o.col);
-			if (want) {
-				int k = 0;
-				while (k < a.nt && tcol[k] != f.b->theap)
-					k++;
-				if (k == a.nt) {
-					tcol[a.nt] = f.b->theap;
-					tw[a.nt++] = o.w;
-					o.track = k + 1;     // the kernel keeps them at this use only
-				}
-			}
-		}
-	}
+	// which sums need their columns' minima and maxima: the shared rule
+	GsTrack tr;
+	gs_plan_sums(sums, nsums, a.n, first, a.s, tr, al, first_use);
+	a.nt = tr.nt;
 	// launch shape as k_ss's: 2 chunks in flight per wave, at most 8
 	// workgroups per CU of 256 CUs
 	constexpr unsigned MAXG = 256u * MGDK_GS_BPC;
@@ -671,42 +595,11 @@ mgdk_select_groupsum_fused(const mgdk_selpred *preds, int npreds, mgdk_bat *s, m
 		return -1;
 	if (h->over || h->ng > GS_MAXG || (int) h->ng > maxgroups)
 		return 1;
-	// every factor's range from the survivors' minimum and maximum (the
-	// type's width where they were not kept): outside lng the operators
-	// raise, or a value would be taken for nil.  Then B = survivors x the
-	// product of the factors' largest magnitudes >= the sum of |term| in any
-	// order, every intermediate product included: below 2^127 nothing can
-	// overflow and the wrapped sums are the true ones
 	uint64_t total = 0;
 	for (uint32_t g = 0; g < h->ng; g++)
 		total += h->cnt[g];
-	for (int j = 0; j < nsums; j++) {
-		uhge bound = total;
-		for (int q = 0; q < sums[j].nf; q++) {
-			const mgdk_gsfactor &f = sums[j].f[q];
-			hge mn = -(hge) (((uhge) 1 << (8 * f.b->twidth - 1)) - 1), mx = -mn;
-			for (int k = 0; k < a.nt; k++)
-				if (tcol[k] == f.b->theap) {
-					mn = h->mn[k];
-					mx = h->mx[k];
-				}
-			if (mn > mx) {               // no live non-nil value: no term
-				bound = 0;
-				continue;
-			}
-			hge lo = mn, hi = mx;
-			if (f.op == '+')
-				lo = (hge) f.cst + mn, hi = (hge) f.cst + mx;
-			else if (f.op == '-')
-				lo = (hge) f.cst - mx, hi = (hge) f.cst - mn;
-			if (f.op && (lo < -(hge) INT64_MAX || hi > (hge) INT64_MAX))
-				return 1;
-			const uhge ml = gs_mag(lo), mh = gs_mag(hi);
-			bound = sat_mul(bound, ml > mh ? ml : mh);
-		}
-		if (bound > lim)
-			return 1;
-	}
+	if (!gs_sums_exact(sums, nsums, total, tr, h->mn, h->mx))
+		return 1;
 	for (uint32_t g = 0; g < h->ng; g++) {
 		mgdk_gsgroup &o = groups[g];
 		memset(&o, 0, sizeof(o));

@@ -84,6 +84,11 @@ class GsGroup(C.Structure):
     _fields_ = [("first", C.c_uint64), ("count", C.c_uint64), ("key", C.c_uint8 * 2), ("_pad", C.c_uint8 * 6)]
 
 
+class GsGroupW(C.Structure):
+    """mgdk_gsgroupw: one group of a select_groupsum_hash."""
+    _fields_ = [("first", C.c_uint64), ("count", C.c_uint64), ("key", C.c_int64 * 2)]
+
+
 class GDKError(RuntimeError):
     pass
 
@@ -270,6 +275,13 @@ _SIGS = {
                                                  C.POINTER(GSumExpr), C.c_int, C.c_int, C.POINTER(C.c_int),
                                                  C.POINTER(GsGroup), C.c_void_p, C.POINTER(C.c_uint64)]),
     "mgdk_select_groupsum_last_lines": (C.c_ulonglong, []),
+    "mgdk_select_groupsum_hash_fused": (C.c_int, [C.POINTER(SelPred), C.c_int, P, C.POINTER(P), C.c_int,
+                                                  C.POINTER(GSumExpr), C.c_int, C.c_int, C.POINTER(C.c_int),
+                                                  C.POINTER(GsGroupW), C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mgdk_select_groupsum_hash_opatatime": (C.c_int, [C.POINTER(SelPred), C.c_int, P, C.POINTER(P), C.c_int,
+                                                      C.POINTER(GSumExpr), C.c_int, C.c_int, C.POINTER(C.c_int),
+                                                      C.POINTER(GsGroupW), C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mgdk_select_groupsum_hash_last_lines": (C.c_ulonglong, []),
     "mgdk_avg3_of_sum": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mgdk_tpch_lineitem": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, PP]),
     "mgdk_gen_window_column": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, PP, PP]),
@@ -1491,6 +1503,13 @@ def select_groupsum(preds, keys, sums, s=None, fused=True, fallback=True, maxgro
     that could overflow, ...) the operators run instead (used_fused False) --
     or, with fallback=False, None is returned and nothing was computed.
     fused=False runs the operators."""
+    return _select_groupsum(lib().mgdk_select_groupsum_fused, lib().mgdk_select_groupsum_opatatime, GsGroup,
+                            preds, keys, sums, s, fused, fallback, maxgroups)
+
+
+def _select_groupsum(fused_fn, ops_fn, group_type, preds, keys, sums, s, fused, fallback, maxgroups):
+    """select_groupsum / select_groupsum_hash: the request as the C entries take it, the
+    fused entry and its op-at-a-time twin, and the groups as dicts."""
     keep = []
     npr, nk, ns = len(preds), len(keys), len(sums)
     cp = _selpreds(preds, keep)
@@ -1510,20 +1529,20 @@ def select_groupsum(preds, keys, sums, s=None, fused=True, fallback=True, maxgro
                 b = f
             cs[j].f[q].b = b.ptr
     ng = C.c_int()
-    grp = (GsGroup * max(1, maxgroups))()
+    grp = (group_type * max(1, maxgroups))()
     res = (C.c_uint64 * (2 * max(1, maxgroups * ns)))()
     nn = (C.c_uint64 * max(1, maxgroups * ns))()
     args = (cp, npr, _p(s), ck, nk, cs, ns, maxgroups, C.byref(ng), grp, C.cast(res, C.c_void_p), nn)
     used = False
     if fused:
-        rc = lib().mgdk_select_groupsum_fused(*args)
+        rc = fused_fn(*args)
         if rc < 0:
             raise _err()
         used = rc == 0
         if not used and not fallback:
             return None
     if not used:
-        _chk(lib().mgdk_select_groupsum_opatatime(*args))
+        _chk(ops_fn(*args))
     out = []
     for i in range(ng.value):
         vals = [hge_to_int(res[2 * (i * ns + j):2 * (i * ns + j) + 2]) for j in range(ns)]
@@ -1537,6 +1556,27 @@ def select_groupsum_last_lines():
     """128-B lines the last fused select_groupsum on this thread read of every
     column but the first predicate's (which is read whole)."""
     return int(lib().mgdk_select_groupsum_last_lines())
+
+
+def select_groupsum_hash(preds, keys, sums, s=None, fused=True, fallback=True, maxgroups=256):
+    """select_groupsum for wider keys and more groups (mgdk_select_groupsum_hash_fused).
+
+    Arguments and result as select_groupsum's.  keys: one or two BATs, each
+    bte, sht, int, lng, date, daytime or timestamp, or str with offsets of 1
+    or 2 bytes and a heap below 64 KiB, their widths together at most 8
+    bytes; `keys` of a group are the full key values (signed ints; the heap
+    offsets for str).  The one-pass kernel takes up to 256 groups; beyond
+    that, for wider keys or where a factor or a sum could overflow, the
+    operators run instead (used_fused False) -- or, with fallback=False, None
+    is returned and nothing was computed."""
+    return _select_groupsum(lib().mgdk_select_groupsum_hash_fused, lib().mgdk_select_groupsum_hash_opatatime,
+                            GsGroupW, preds, keys, sums, s, fused, fallback, maxgroups)
+
+
+def select_groupsum_hash_last_lines():
+    """128-B lines the last fused select_groupsum_hash on this thread read of
+    every column but the first predicate's (which is read whole)."""
+    return int(lib().mgdk_select_groupsum_hash_last_lines())
 
 
 def avg3_of_sum(total, n):

@@ -65,6 +65,9 @@ def ALGthetaselect2(gdk, b, s, val, op):
 # (None: the nil of the column's type).  The ":type" suffix is the MAL result
 # type, as in `batcalc.*(pa, pb):hge`.
 
+# run_plan's default for the hashed grouped route: DESIGN.md 11.12
+HASHED_DEFAULT = True
+
 SELECTS = ("algebra.select", "algebra.thetaselect")
 FUSED = ("mgdk.select_sum", "mgdk.select_groupsum")
 
@@ -110,7 +113,7 @@ def _nil_to_none(gdk, v):
     return None if v == gdk.NIL[gdk.TYPE_hge] else v
 
 
-def _run_one(gdk, ins, env):
+def _run_one(gdk, ins, env, hashed=False):
     res, fn, args = ins
     name, tp = _split(fn)
     isvar = (lambda a: isinstance(a, str) and a in env)
@@ -148,7 +151,7 @@ def _run_one(gdk, ins, env):
             env[r] = o
         return
     elif name == "mgdk.select_groupsum":
-        _run_select_groupsum(gdk, ins, env)
+        _run_select_groupsum(gdk, ins, env, hashed)
         return
     elif name.startswith("batcalc.") and name[8:] in ("*", "+", "-"):
         if tp != "hge":
@@ -193,7 +196,7 @@ def _run_select_sum(gdk, ins, env):
         _run_one(gdk, k, env)
 
 
-def run_plan(gdk, plan, env=None, fuse=True):
+def run_plan(gdk, plan, env=None, fuse=True, hashed=None):
     """Execute a plan against a GDK binding (monetdb_amd.gdk or the
     oracle's Python module); returns the variables, `env` included.  Executed:
     algebra.select / thetaselect / projection, batcalc.* / + / - into hge,
@@ -203,12 +206,16 @@ def run_plan(gdk, plan, env=None, fuse=True):
     that fuse_select_sum / fuse_select_groupsum put in.  fuse=True (the
     default: the fused operators beat the operators where they were measured,
     DESIGN.md 11.10, 11.11) applies those rewrites first; a plan that is
-    already rewritten is left as it is."""
+    already rewritten is left as it is.  hashed: a mgdk.select_groupsum whose
+    keys are wider than a byte, or that the narrow operator declined, tries
+    the binding's select_groupsum_hash before the kept instructions (None:
+    HASHED_DEFAULT, which follows the measurement of DESIGN.md 11.12)."""
+    hashed = HASHED_DEFAULT if hashed is None else hashed
     env = dict(env or {})
     if fuse:
         plan = fuse_select_groupsum(fuse_select_sum(plan))
     for ins in plan:
-        _run_one(gdk, ins, env)
+        _run_one(gdk, ins, env, hashed)
     return env
 
 
@@ -321,11 +328,19 @@ def fuse_select_sum(plan):
 GS_MAXKEYS, GS_MAXSUMS, GS_MAXFACTORS = 2, 6, 3
 
 
-def _run_select_groupsum(gdk, ins, env):
+def _twidth(b):
+    s = b.s
+    return s.twidth if hasattr(s, "twidth") else s.width
+
+
+def _run_select_groupsum(gdk, ins, env, hashed=False):
     """mgdk.select_groupsum: the fused operator where the binding has one and
     it applies -- its group results then stand in for the aggr.sub* results and
     for the projections through the extents -- otherwise the instructions the
-    rewrite replaced."""
+    rewrite replaced.  The routes in order: select_groupsum where every key is
+    one byte wide; where it declines, and for wider keys at once,
+    select_groupsum_hash if the binding has it and `hashed` allows it; the
+    kept instructions."""
     res, _, (spec,) = ins
     r = None
     if hasattr(gdk, "select_groupsum"):
@@ -337,7 +352,10 @@ def _run_select_groupsum(gdk, ins, env):
         sums = [tuple(env[f] if isinstance(f, str) else (f[0], f[1], env[f[2]]) for f in fs)
                 for fs in spec["sums"]]
         s = env[spec["s"]] if spec["s"] is not None else None
-        r = gdk.select_groupsum(preds, keys, sums, s, fused=True, fallback=False)
+        if all(_twidth(k) == 1 for k in keys):
+            r = gdk.select_groupsum(preds, keys, sums, s, fused=True, fallback=False)
+        if r is None and hashed and hasattr(gdk, "select_groupsum_hash"):
+            r = gdk.select_groupsum_hash(preds, keys, sums, s, fused=True, fallback=False)
     if r is None:
         for k in spec["kept"]:
             _run_one(gdk, k, env)
