@@ -643,6 +643,55 @@ int mgdk_select_groupsum_hash_opatatime(const mgdk_selpred *preds, int npreds, m
 /* as mgdk_select_groupsum_last_lines, for the calling thread's last
  * mgdk_select_groupsum_hash_fused; a key column of width w counts as any column of that width */
 unsigned long long mgdk_select_groupsum_hash_last_lines(void);
+/* ---- the same fragment over a star join: a predicate, key or factor column
+ *      may belong to a dimension table and be reached through a join index,
+ *      an oid column `via` of the fact table whose values are row ids of the
+ *      dimension (sql.bind_idxbat).  A column b whose
+ *      descriptor is some vias[i].col is such a dimension column, reached
+ *      through V = vias[i].via (by descriptor, not by heap: a second
+ *      descriptor over one heap is a second route); every other column is a
+ *      fact column.  All fact columns and all vias have one count and
+ *      hseqbase; a via has ttype oid and may hold nil oids; a dimension
+ *      column has a count (below 2^31) and hseqbase of its own and is
+ *      otherwise what mgdk_select_groupsum_hash_fused takes in its position.
+ *      nvias is 0..16.
+ *      With x(c, b) = BATproject(c, b) for a fact column and
+ *      BATproject(BATproject(c, V), b) for a dimension column: predicate i on
+ *      a fact column is c_i = BATselect / BATthetaselect(b, c_{i-1}, ...); on
+ *      a dimension column p = BATselect / BATthetaselect(x(c_{i-1}, b), NULL,
+ *      ...) and c_i = BATproject(p, c_{i-1}) (c_{i-1} NULL: x is
+ *      BATproject(V, b) and c_i is p at the fact table's hseqbase); keys are
+ *      x(c, keys[j]), factors x(c, col) or cst +- x(c, col); the rest is the
+ *      hashed entry's.  BATproject's rules hold: a nil oid gives the
+ *      dimension type's nil (and is refused for a str key), an oid outside the
+ *      dimension is an error.  The fused entry answers 1 where a row that is
+ *      live at that step holds such an oid -- the operators then raise -- and
+ *      is not affected by one in a row an earlier predicate removed.  A
+ *      predicate on a dimension column selects on values that hold a nil per
+ *      nil oid, whatever the column's own tnonil; one that BATselect decides
+ *      without a scan, or a predicate no row can pass after one on a
+ *      dimension column, answers 1, since the operators project first.
+ *      Returns as mgdk_select_groupsum_hash_fused; with nvias == 0 its
+ *      results, bit for bit ----------------------------------------------- */
+typedef struct mgdk_starvia { mgdk_bat *col; mgdk_bat *via; } mgdk_starvia;
+int mgdk_select_groupsum_star_fused(const mgdk_selpred *preds, int npreds, mgdk_bat *s,
+				    mgdk_bat *const *keys, int nkeys, const mgdk_gsumexpr *sums, int nsums,
+				    const mgdk_starvia *vias, int nvias,
+				    int maxgroups, int *ngroups, mgdk_gsgroupw *groups,
+				    void *sumres, uint64_t *nonnil);
+/* the chain above through the operators, literally; never returns 1 */
+int mgdk_select_groupsum_star_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s,
+					mgdk_bat *const *keys, int nkeys, const mgdk_gsumexpr *sums, int nsums,
+					const mgdk_starvia *vias, int nvias,
+					int maxgroups, int *ngroups, mgdk_gsgroupw *groups,
+					void *sumres, uint64_t *nonnil);
+/* for the calling thread's last mgdk_select_groupsum_star_fused: the 128-byte
+ * lines as mgdk_select_groupsum_hash_last_lines counts them, a join index
+ * counting as an 8-byte column at its first use and a dimension column not at
+ * all; and the elements gathered from dimension columns, one per use and live
+ * row with a non-nil oid */
+unsigned long long mgdk_select_groupsum_star_last_lines(void);
+unsigned long long mgdk_select_groupsum_star_last_gathers(void);
 /* BATgroupavg3's average (rounded half away from zero) and remainder of one
  * group from its exact sum (16 bytes, hge) and its count n > 0; -1 when n <= 0 */
 int mgdk_avg3_of_sum(const void *sum_hge, int64_t n, int64_t *avg, int64_t *rem);

@@ -243,12 +243,16 @@ select_sum_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s, const m
 // BATgroupcount, and the keys and first rows through the extents.  G is
 // mgdk_gsgroup (the keys' bytes) or mgdk_gsgroupw (the hashed entry's twin:
 // the keys read back at their own width, sign-extended, str offsets
-// zero-extended)
+// zero-extended).  vias (mgdk_select_groupsum_star_opatatime): a column whose
+// descriptor is some vias[i].col belongs to a dimension table and is reached
+// through the join index V = vias[i].via: two projections where a fact column
+// takes one, and a predicate on it selects on the gathered values without a
+// candidate list and takes its result through the previous candidate list
 template <typename G>
 int
 select_groupsum_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s, mgdk_bat *const *keys, int nkeys,
 			  const mgdk_gsumexpr *sums, int nsums, int maxgroups, int *ngroups, G *groups,
-			  void *sumres, uint64_t *nonnil)
+			  void *sumres, uint64_t *nonnil, const mgdk_starvia *vias = nullptr, int nvias = 0)
 {
 	constexpr bool WIDE = sizeof(((G *) nullptr)->key[0]) == 8;
 	if (keys == nullptr || nkeys < 1 || nkeys > 2 || keys[0] == nullptr || ngroups == nullptr || npreds < 0 ||
@@ -256,19 +260,54 @@ select_groupsum_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s, mg
 		seterr("select_groupsum: one or two key columns are required");
 		return -1;
 	}
+	if (nvias < 0 || (nvias > 0 && vias == nullptr)) {
+		seterr("select_groupsum: the join indexes are missing");
+		return -1;
+	}
+	for (int i = 0; i < nvias; i++)
+		if (vias[i].col == nullptr || vias[i].via == nullptr) {
+			seterr("select_groupsum: a join index names a dimension column and an oid column");
+			return -1;
+		}
 	Bats t;
+	auto via_of = [&](const mgdk_bat *b) -> mgdk_bat * {
+		for (int i = 0; i < nvias; i++)
+			if (vias[i].col == b)
+				return vias[i].via;
+		return nullptr;
+	};
+	// x(c, b): b's values at the candidates c
+	auto project = [&](mgdk_bat *c, mgdk_bat *b) -> mgdk_bat * {
+		mgdk_bat *v = via_of(b);
+		if (v == nullptr)
+			return t.add(mgdk_BATproject(c, b));
+		mgdk_bat *o = t.add(mgdk_BATproject(c, v));
+		return o ? t.add(mgdk_BATproject(o, b)) : nullptr;
+	};
 	mgdk_bat *c = s;
 	for (int i = 0; i < npreds; i++) {
 		const mgdk_selpred &p = preds[i];
-		c = t.add(p.op ? mgdk_BATthetaselect(p.b, c, p.tl, p.op)
-			       : mgdk_BATselect(p.b, c, p.tl, p.th, p.li, p.hi, p.anti, p.nil_matches));
-		if (!c)
+		mgdk_bat *v = p.b ? via_of(p.b) : nullptr, *b = p.b, *cand = c;
+		if (v) {
+			// BATproject keeps its left operand's head: without a
+			// candidate list the selected oids are the fact table's
+			b = c ? project(c, p.b) : t.add(mgdk_BATproject(v, p.b));
+			cand = nullptr;
+			if (!b)
+				return -1;
+		}
+		mgdk_bat *r = t.add(p.op ? mgdk_BATthetaselect(b, cand, p.tl, p.op)
+					 : mgdk_BATselect(b, cand, p.tl, p.th, p.li, p.hi, p.anti, p.nil_matches));
+		if (r && v && c)
+			r = t.add(mgdk_BATproject(r, c));
+		if (!(c = r))
 			return -1;
 	}
 	if (c == nullptr) {
 		// no select at all: every row of the keys
 		Cand ci;
-		if (cand_init(&ci, keys[0], nullptr) < 0 || !(c = t.add(cand_slice(ci))))
+		mgdk_bat *v = via_of(keys[0]);
+		if (cand_init(&ci, v ? v : keys[0], nullptr) < 0 || !(c = t.add(cand_slice(ci))))
 			return -1;
 	}
 	mgdk_bat *g = nullptr, *e = nullptr, *h = nullptr, *k[2] = {nullptr, nullptr};
@@ -282,7 +321,7 @@ select_groupsum_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s, mg
 			seterr("select_groupsum: a key column of width %d does not fit the result's keys", (int) keys[j]->twidth);
 			return -1;
 		}
-		if (!(k[j] = t.add(mgdk_BATproject(c, keys[j]))))
+		if (!(k[j] = project(c, keys[j])))
 			return -1;
 		if (k[j]->count != 0 && !fits(k[j]->twidth)) {
 			seterr("select_groupsum: a key column of width %d does not fit the result's keys", (int) k[j]->twidth);
@@ -307,7 +346,7 @@ select_groupsum_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s, mg
 		mgdk_bat *x = nullptr;
 		for (int q = 0; q < sums[j].nf; q++) {
 			const mgdk_gsfactor &f = sums[j].f[q];
-			mgdk_bat *v = f.b ? t.add(mgdk_BATproject(c, f.b)) : nullptr;
+			mgdk_bat *v = f.b ? project(c, f.b) : nullptr;
 			if (v && f.op == '+')
 				v = t.add(mgdk_BATcalccstadd(&f.cst, MGDK_lng, v, nullptr, MGDK_lng));
 			else if (v && f.op == '-')
@@ -389,6 +428,15 @@ int mgdk_select_groupsum_hash_opatatime(const mgdk_selpred *preds, int npreds, m
 {
 	return select_groupsum_opatatime(preds, npreds, s, keys, nkeys, sums, nsums, maxgroups, ngroups, groups, sumres,
 					 nonnil);
+}
+
+int mgdk_select_groupsum_star_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s, mgdk_bat *const *keys,
+					int nkeys, const mgdk_gsumexpr *sums, int nsums, const mgdk_starvia *vias,
+					int nvias, int maxgroups, int *ngroups, mgdk_gsgroupw *groups, void *sumres,
+					uint64_t *nonnil)
+{
+	return select_groupsum_opatatime(preds, npreds, s, keys, nkeys, sums, nsums, maxgroups, ngroups, groups, sumres,
+					 nonnil, vias, nvias);
 }
 
 int mgdk_select_sum_opatatime(const mgdk_selpred *preds, int npreds, mgdk_bat *s, const mgdk_sumexpr *sums,

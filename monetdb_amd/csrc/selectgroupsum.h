@@ -1,5 +1,5 @@
 // selectgroupsum.h -- what the two fused select-cascade GROUP BY kernels share
-// (selectgroupsum.hip: one-byte keys, 8 groups; selectgroupsum_hash.hip: keys
+// (selectgroupsum.hip: one-byte keys, 8 groups; selectgroupsum_hash.h: keys
 // of up to 8 bytes together, 256 groups): the sum / factor descriptions, the
 // 128-bit add, and the host-side overflow rule -- which columns need their
 // minimum and maximum kept, and the final check of the factors' ranges and of
@@ -25,9 +25,12 @@ struct GsS {
 	GsF f[GS_MAXF];
 	int nf, pad;
 };
-// the columns whose minimum and maximum over the live non-nil rows are kept
+// the columns whose minimum and maximum over the live non-nil rows are kept.
+// A column reached through a join index (selectgroupsum_hash.h) is the pair
+// of both heaps -- the values its live rows gather -- and via is NULL for a
+// column of the table itself
 struct GsTrack {
-	const void *col[GS_MAXT];
+	const void *col[GS_MAXT], *via[GS_MAXT];
 	int w[GS_MAXT];
 	int nt;
 };
@@ -81,11 +84,13 @@ gs_sums_ok(const mgdk_gsumexpr *sums, int nsums, Same same)
 // where that bounds every factor within lng and rows x the product of the
 // factors' magnitudes below 2^127, the sum needs no minima and maxima;
 // otherwise each of its columns is tracked (at its first such use).  `al`
-// is cleared when an operand does not start 16-byte aligned.
-template <typename FirstUse>
+// is cleared when an operand does not start 16-byte aligned.  via_of(b): the
+// join index through which b is reached, NULL for a column of the table; such
+// a b starts at its own first row and need not be aligned.
+template <typename FirstUse, typename ViaOf>
 inline void
 gs_plan_sums(const mgdk_gsumexpr *sums, int nsums, uint64_t rows, uint64_t first, GsS *out, GsTrack &tr, bool &al,
-	     FirstUse first_use)
+	     FirstUse first_use, ViaOf via_of)
 {
 	constexpr uhge lng_max = (uhge) INT64_MAX;
 	tr.nt = 0;
@@ -106,19 +111,22 @@ gs_plan_sums(const mgdk_gsumexpr *sums, int nsums, uint64_t rows, uint64_t first
 		for (int q = 0; q < x.nf; q++) {
 			const mgdk_gsfactor &f = sums[j].f[q];
 			GsF &o = x.f[q];
+			const mgdk_bat *via = via_of(f.b);
+			const void *vh = via ? via->theap : nullptr;
 			o.w = f.b->twidth;
-			o.col = (const char *) f.b->theap + first * (uint64_t) o.w;
+			o.col = (const char *) f.b->theap + (via ? 0 : first * (uint64_t) o.w);
 			o.op = f.op;
 			o.cst = f.cst;
 			o.nil = ss_nil(o.w);
 			o.count = first_use(f.b);
-			al = al && aligned16(o.col);
+			al = al && (via || aligned16(o.col));
 			if (want) {
 				int k = 0;
-				while (k < tr.nt && tr.col[k] != f.b->theap)
+				while (k < tr.nt && (tr.col[k] != f.b->theap || tr.via[k] != vh))
 					k++;
 				if (k == tr.nt) {
 					tr.col[tr.nt] = f.b->theap;
+					tr.via[tr.nt] = vh;
 					tr.w[tr.nt++] = o.w;
 					o.track = k + 1;     // the kernel keeps them at this use only
 				}
@@ -127,23 +135,40 @@ gs_plan_sums(const mgdk_gsumexpr *sums, int nsums, uint64_t rows, uint64_t first
 	}
 }
 
+inline const mgdk_bat *
+gs_no_via(const mgdk_bat *)
+{
+	return nullptr;
+}
+
+template <typename FirstUse>
+inline void
+gs_plan_sums(const mgdk_gsumexpr *sums, int nsums, uint64_t rows, uint64_t first, GsS *out, GsTrack &tr, bool &al,
+	     FirstUse first_use)
+{
+	gs_plan_sums(sums, nsums, rows, first, out, tr, al, first_use, gs_no_via);
+}
+
 // every factor's range from the survivors' minimum and maximum (the type's
 // width where they were not kept): outside lng the operators raise, or a
 // value would be taken for nil.  Then B = survivors x the product of the
 // factors' largest magnitudes >= the sum of |term| in any order, every
 // intermediate product included: below 2^127 nothing can overflow and the
 // wrapped sums are the true ones.  false: the operators have to answer
+template <typename ViaOf>
 inline bool
 gs_sums_exact(const mgdk_gsumexpr *sums, int nsums, uint64_t survivors, const GsTrack &tr, const long long *mns,
-	      const long long *mxs)
+	      const long long *mxs, ViaOf via_of)
 {
 	for (int j = 0; j < nsums; j++) {
 		uhge bound = survivors;
 		for (int q = 0; q < sums[j].nf; q++) {
 			const mgdk_gsfactor &f = sums[j].f[q];
 			hge mn = -(hge) (((uhge) 1 << (8 * f.b->twidth - 1)) - 1), mx = -mn;
+			const mgdk_bat *via = via_of(f.b);
+			const void *vh = via ? via->theap : nullptr;
 			for (int k = 0; k < tr.nt; k++)
-				if (tr.col[k] == f.b->theap) {
+				if (tr.col[k] == f.b->theap && tr.via[k] == vh) {
 					mn = mns[k];
 					mx = mxs[k];
 				}
@@ -165,6 +190,13 @@ gs_sums_exact(const mgdk_gsumexpr *sums, int nsums, uint64_t survivors, const Gs
 			return false;
 	}
 	return true;
+}
+
+inline bool
+gs_sums_exact(const mgdk_gsumexpr *sums, int nsums, uint64_t survivors, const GsTrack &tr, const long long *mns,
+	      const long long *mxs)
+{
+	return gs_sums_exact(sums, nsums, survivors, tr, mns, mxs, gs_no_via);
 }
 
 }  // namespace

@@ -205,10 +205,12 @@ ss_nil(int w)
 }
 
 // one predicate through BATselect's normalisation: the outcome, or -1 when
-// the operators have to answer (an argument they reject)
+// the operators have to answer (an argument they reject).  tnonil: whether
+// the values selected on are known to hold no nil -- the column's own
+// property, except where they are gathered through a join index
 template <typename T>
 int
-ss_normalise(const mgdk_selpred &p, SsP *o)
+ss_normalise(const mgdk_selpred &p, SsP *o, bool tnonil)
 {
 	const void *tl = p.tl, *th = p.th;
 	bool li = p.li, hi = p.hi, anti = p.anti, nil_matches = p.nil_matches;
@@ -224,7 +226,7 @@ ss_normalise(const mgdk_selpred &p, SsP *o)
 		tl = ta.tl, th = ta.th, li = ta.li, hi = ta.hi, anti = ta.anti, nil_matches = ta.nil_matches;
 	}
 	SelPred<T> sp{};
-	const SelOutcome r = sel_normalise<T>(p.b->tnonil, (const T *) tl, (const T *) th, li, hi, anti, nil_matches, &sp);
+	const SelOutcome r = sel_normalise<T>(tnonil, (const T *) tl, (const T *) th, li, hi, anti, nil_matches, &sp);
 	o->mode = sp.mode;
 	o->nil_matches = sp.nil_matches;
 	o->vl = (int64_t) sp.vl;
@@ -233,16 +235,29 @@ ss_normalise(const mgdk_selpred &p, SsP *o)
 	return r;
 }
 
+template <typename T>
+int
+ss_normalise(const mgdk_selpred &p, SsP *o)
+{
+	return ss_normalise<T>(p, o, p.b->tnonil != 0);
+}
+
 // ss_normalise at the predicate column's width
+inline int
+ss_normalise_w(const mgdk_selpred &p, SsP *o, bool tnonil)
+{
+	switch (p.b->twidth) {
+	case 1: return ss_normalise<int8_t>(p, o, tnonil);
+	case 2: return ss_normalise<int16_t>(p, o, tnonil);
+	case 4: return ss_normalise<int32_t>(p, o, tnonil);
+	default: return ss_normalise<int64_t>(p, o, tnonil);
+	}
+}
+
 inline int
 ss_normalise_w(const mgdk_selpred &p, SsP *o)
 {
-	switch (p.b->twidth) {
-	case 1: return ss_normalise<int8_t>(p, o);
-	case 2: return ss_normalise<int16_t>(p, o);
-	case 4: return ss_normalise<int32_t>(p, o);
-	default: return ss_normalise<int64_t>(p, o);
-	}
+	return ss_normalise_w(p, o, p.b->tnonil != 0);
 }
 
 }  // namespace

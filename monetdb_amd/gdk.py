@@ -89,6 +89,11 @@ class GsGroupW(C.Structure):
     _fields_ = [("first", C.c_uint64), ("count", C.c_uint64), ("key", C.c_int64 * 2)]
 
 
+class StarVia(C.Structure):
+    """mgdk_starvia: a dimension column and the join index that leads to it."""
+    _fields_ = [("col", P), ("via", P)]
+
+
 class GDKError(RuntimeError):
     pass
 
@@ -282,6 +287,16 @@ _SIGS = {
                                                       C.POINTER(GSumExpr), C.c_int, C.c_int, C.POINTER(C.c_int),
                                                       C.POINTER(GsGroupW), C.c_void_p, C.POINTER(C.c_uint64)]),
     "mgdk_select_groupsum_hash_last_lines": (C.c_ulonglong, []),
+    "mgdk_select_groupsum_star_fused": (C.c_int, [C.POINTER(SelPred), C.c_int, P, C.POINTER(P), C.c_int,
+                                                  C.POINTER(GSumExpr), C.c_int, C.POINTER(StarVia), C.c_int, C.c_int,
+                                                  C.POINTER(C.c_int), C.POINTER(GsGroupW), C.c_void_p,
+                                                  C.POINTER(C.c_uint64)]),
+    "mgdk_select_groupsum_star_opatatime": (C.c_int, [C.POINTER(SelPred), C.c_int, P, C.POINTER(P), C.c_int,
+                                                      C.POINTER(GSumExpr), C.c_int, C.POINTER(StarVia), C.c_int,
+                                                      C.c_int, C.POINTER(C.c_int), C.POINTER(GsGroupW), C.c_void_p,
+                                                      C.POINTER(C.c_uint64)]),
+    "mgdk_select_groupsum_star_last_lines": (C.c_ulonglong, []),
+    "mgdk_select_groupsum_star_last_gathers": (C.c_ulonglong, []),
     "mgdk_avg3_of_sum": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mgdk_tpch_lineitem": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, PP]),
     "mgdk_gen_window_column": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, PP, PP]),
@@ -1507,9 +1522,10 @@ def select_groupsum(preds, keys, sums, s=None, fused=True, fallback=True, maxgro
                             preds, keys, sums, s, fused, fallback, maxgroups)
 
 
-def _select_groupsum(fused_fn, ops_fn, group_type, preds, keys, sums, s, fused, fallback, maxgroups):
-    """select_groupsum / select_groupsum_hash: the request as the C entries take it, the
-    fused entry and its op-at-a-time twin, and the groups as dicts."""
+def _select_groupsum(fused_fn, ops_fn, group_type, preds, keys, sums, s, fused, fallback, maxgroups, vias=None):
+    """select_groupsum / select_groupsum_hash / select_groupsum_star: the request as the C
+    entries take it, the fused entry and its op-at-a-time twin, and the groups as dicts.
+    vias (the star entries only): (dimension column, join index) pairs, passed after the sums."""
     keep = []
     npr, nk, ns = len(preds), len(keys), len(sums)
     cp = _selpreds(preds, keep)
@@ -1532,7 +1548,13 @@ def _select_groupsum(fused_fn, ops_fn, group_type, preds, keys, sums, s, fused, 
     grp = (group_type * max(1, maxgroups))()
     res = (C.c_uint64 * (2 * max(1, maxgroups * ns)))()
     nn = (C.c_uint64 * max(1, maxgroups * ns))()
-    args = (cp, npr, _p(s), ck, nk, cs, ns, maxgroups, C.byref(ng), grp, C.cast(res, C.c_void_p), nn)
+    extra = ()
+    if vias is not None:
+        cv = (StarVia * max(1, len(vias)))()
+        for i, (col, via) in enumerate(vias):
+            cv[i].col, cv[i].via = col.ptr, via.ptr
+        extra = (cv, len(vias))
+    args = (cp, npr, _p(s), ck, nk, cs, ns) + extra + (maxgroups, C.byref(ng), grp, C.cast(res, C.c_void_p), nn)
     used = False
     if fused:
         rc = fused_fn(*args)
@@ -1577,6 +1599,35 @@ def select_groupsum_hash_last_lines():
     """128-B lines the last fused select_groupsum_hash on this thread read of
     every column but the first predicate's (which is read whole)."""
     return int(lib().mgdk_select_groupsum_hash_last_lines())
+
+
+def select_groupsum_star(preds, keys, sums, vias, s=None, fused=True, fallback=True, maxgroups=256):
+    """select_groupsum_hash over a star join (mgdk_select_groupsum_star_fused).
+
+    vias: a list of (col, via) BAT pairs.  A BAT that is the `col` of a pair
+    (the same Python-side descriptor, not merely the same data) belongs to a
+    dimension table and is reached through `via`, an oid column of the fact
+    table holding row ids of the dimension (a join index); it may stand as a
+    predicate's column, as a key or in a factor.  Every other BAT is a column
+    of the fact table.  A nil oid yields nil, as BATproject does.  An oid
+    that no row of the dimension has, in a row that is still live where the
+    column is used, is the operators' error: the fused kernel declines such
+    a request.  Arguments otherwise, result and `fallback` as
+    select_groupsum_hash's."""
+    return _select_groupsum(lib().mgdk_select_groupsum_star_fused, lib().mgdk_select_groupsum_star_opatatime,
+                            GsGroupW, preds, keys, sums, s, fused, fallback, maxgroups, vias=list(vias))
+
+
+def select_groupsum_star_last_lines():
+    """128-B lines the last fused select_groupsum_star on this thread read of every
+    fact column but the first predicate's, a join index counting as an 8-byte column."""
+    return int(lib().mgdk_select_groupsum_star_last_lines())
+
+
+def select_groupsum_star_last_gathers():
+    """Elements the last fused select_groupsum_star on this thread gathered from dimension
+    columns: one per use and live row whose oid is not nil."""
+    return int(lib().mgdk_select_groupsum_star_last_gathers())
 
 
 def avg3_of_sum(total, n):

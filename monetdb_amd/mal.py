@@ -67,6 +67,8 @@ def ALGthetaselect2(gdk, b, s, val, op):
 
 # run_plan's default for the hashed grouped route: DESIGN.md 11.12
 HASHED_DEFAULT = True
+# run_plan's default for the star rewrite (fuse_star_groupsum): DESIGN.md 11.13
+STAR_DEFAULT = True
 
 SELECTS = ("algebra.select", "algebra.thetaselect")
 FUSED = ("mgdk.select_sum", "mgdk.select_groupsum")
@@ -125,6 +127,15 @@ def _run_one(gdk, ins, env, hashed=False):
         out = gdk.BATthetaselect(b, s, *call) if name == "algebra.thetaselect" else gdk.BATselect(b, s, *call)
     elif name == "algebra.projection":
         out = gdk.BATproject(val(args[0]), val(args[1]))
+    elif name == "algebra.projectionpath":
+        # BATprojectchain on the product; nested BATprojects where a binding lacks it
+        bats = [val(a) for a in args]
+        if hasattr(gdk, "BATprojectchain"):
+            out = gdk.BATprojectchain(bats)
+        else:
+            out = bats[0]
+            for b in bats[1:]:
+                out = gdk.BATproject(out, b)
     elif name in ("group.group", "group.subgroup"):
         b = val(args[0])
         g = val(args[1]) if name == "group.subgroup" else None
@@ -196,7 +207,7 @@ def _run_select_sum(gdk, ins, env):
         _run_one(gdk, k, env)
 
 
-def run_plan(gdk, plan, env=None, fuse=True, hashed=None):
+def run_plan(gdk, plan, env=None, fuse=True, hashed=None, star=None):
     """Execute a plan against a GDK binding (monetdb_amd.gdk or the
     oracle's Python module); returns the variables, `env` included.  Executed:
     algebra.select / thetaselect / projection, batcalc.* / + / - into hge,
@@ -209,11 +220,17 @@ def run_plan(gdk, plan, env=None, fuse=True, hashed=None):
     already rewritten is left as it is.  hashed: a mgdk.select_groupsum whose
     keys are wider than a byte, or that the narrow operator declined, tries
     the binding's select_groupsum_hash before the kept instructions (None:
-    HASHED_DEFAULT, which follows the measurement of DESIGN.md 11.12)."""
+    HASHED_DEFAULT, which follows the measurement of DESIGN.md 11.12).  star:
+    the grouped rewrite is fuse_star_groupsum, which also takes fragments with
+    columns gathered through a join index to the binding's
+    select_groupsum_star (None: STAR_DEFAULT); a plan without
+    such a column is rewritten and run the same either way.
+    algebra.projectionpath is executed as well."""
     hashed = HASHED_DEFAULT if hashed is None else hashed
+    star = STAR_DEFAULT if star is None else star
     env = dict(env or {})
     if fuse:
-        plan = fuse_select_groupsum(fuse_select_sum(plan))
+        plan = (fuse_star_groupsum if star else fuse_select_groupsum)(fuse_select_sum(plan))
     for ins in plan:
         _run_one(gdk, ins, env, hashed)
     return env
@@ -343,6 +360,9 @@ def _run_select_groupsum(gdk, ins, env, hashed=False):
     kept instructions."""
     res, _, (spec,) = ins
     r = None
+    if spec.get("vias"):
+        _run_select_groupsum_star(gdk, ins, env)
+        return
     if hasattr(gdk, "select_groupsum"):
         preds = []
         for fn, col, rest in spec["preds"]:
@@ -360,7 +380,43 @@ def _run_select_groupsum(gdk, ins, env, hashed=False):
         for k in spec["kept"]:
             _run_one(gdk, k, env)
         return
-    groups, _ = r
+    _groupsum_outs(gdk, spec, r[0], env, env)
+
+
+def _run_select_groupsum_star(gdk, ins, env):
+    """A mgdk.select_groupsum whose spec carries `vias` ({route: (dimension
+    column, join index)}): the binding's select_groupsum_star where it has one
+    and every join index is an oid column, then the kept instructions.  Each
+    route gets a descriptor of its own: the dimension column's for the first
+    route to it, a view of it for a further one."""
+    res, _, (spec,) = ins
+    r = None
+    vias = spec["vias"]
+    if hasattr(gdk, "select_groupsum_star") and all(_ttype(env[v]) == gdk.TYPE_oid for _, v in vias.values()):
+        cols, taken = dict(env), set()
+        for rid, (d, v) in vias.items():
+            cols[rid] = env[d] if d not in taken else gdk.BATslice(env[d], 0, env[d].count())
+            taken.add(d)
+        preds = []
+        for fn, col, rest in spec["preds"]:
+            preds.append((cols[col],) + tuple(_pred_call(gdk, cols[col], fn, rest)))
+        keys = [cols[k] for k in spec["keys"]]
+        sums = [tuple(cols[f] if isinstance(f, str) else (f[0], f[1], cols[f[2]]) for f in fs)
+                for fs in spec["sums"]]
+        s = env[spec["s"]] if spec["s"] is not None else None
+        r = gdk.select_groupsum_star(preds, keys, sums, [(cols[rid], env[v]) for rid, (d, v) in vias.items()], s,
+                                     fused=True, fallback=False)
+    if r is None:
+        for k in spec["kept"]:
+            _run_one(gdk, k, env)
+        return
+    _groupsum_outs(gdk, spec, r[0], env, cols)
+
+
+def _groupsum_outs(gdk, spec, groups, env, cols):
+    """The results of a mgdk.select_groupsum from the fused operator's groups;
+    cols: the columns by the names the spec uses."""
+    vias = spec.get("vias") or {}
     lng = (lambda vals: gdk.BAT.from_numpy(gdk.TYPE_lng, [gdk.NIL[gdk.TYPE_lng] if v is None else v for v in vals]))
     first = gdk.BAT.from_numpy(gdk.TYPE_oid, [g["first"] for g in groups])
     for out in spec["outs"]:
@@ -375,7 +431,7 @@ def _run_select_groupsum(gdk, ins, env, hashed=False):
             # BATgroupavg3 of the column from its exact sum: a group without
             # a non-nil value has a nil average, remainder 0 and count 0
             (a, rm, n), j, col = out[1], out[2], out[3]
-            tp = _ttype(env[col])
+            tp = _ttype(cols[col])
             trip = [gdk.avg3_of_sum(g["sums"][j], g["nonnil"][j]) if g["nonnil"][j] else (gdk.NIL[tp], 0)
                     for g in groups]
             env[a] = gdk.BAT.from_numpy(tp, [t[0] for t in trip])
@@ -383,6 +439,9 @@ def _run_select_groupsum(gdk, ins, env, hashed=False):
             env[n] = lng([g["nonnil"][j] for g in groups])
         elif kind == "first":
             env[out[1]] = first
+        elif out[2] in vias:            # "proj" of a gathered column: through its join index
+            d, v = vias[out[2]]
+            env[out[1]] = gdk.BATproject(gdk.BATproject(first, env[v]), env[d])
         else:                           # "proj": a column at the groups' first rows
             env[out[1]] = gdk.BATproject(first, env[out[2]])
 
@@ -407,6 +466,30 @@ def fuse_select_groupsum(plan):
     candidate list, projection, factor, product, group-id BAT and histogram is
     used inside the fragment only and the final extents feed nothing but the
     aggregates and such projections."""
+    return _fuse_groupsum(plan, False)
+
+
+def fuse_star_groupsum(plan):
+    """fuse_select_groupsum for star joins: the same fragment, in which a key,
+    an operand or a predicate's column may be gathered through a join index V
+    (an oid column of the fact table, checked when the plan runs) from a column
+    D of a dimension table, V and D plan inputs:
+
+        t := algebra.projection(c, V);  x := algebra.projection(t, D)      a gathered value, or
+        x := algebra.projectionpath(c, V, D)
+        p := algebra.select | algebra.thetaselect(x, ...)                  a gathered predicate: x taken from
+        c_i := algebra.projection(p, c_{i-1})                              c_{i-1}, no candidate list in the select
+
+    The emitted mgdk.select_groupsum names a gathered column by its route and
+    its spec carries "vias": {route: (D, V)}; run_plan takes such a spec to
+    the binding's select_groupsum_star, then to the kept instructions.  A plan
+    whose first select is on a gathered column without a candidate-list
+    variable before it is left as written; a fragment without a gathered
+    column is rewritten exactly as fuse_select_groupsum does."""
+    return _fuse_groupsum(plan, True)
+
+
+def _fuse_groupsum(plan, star):
     plan = list(plan)
     defs, uses = {}, {}
     for i, (res, fn, args) in enumerate(plan):
@@ -425,7 +508,7 @@ def fuse_select_groupsum(plan):
     for i0 in range(len(plan)):
         if name_of(i0) != "group.group" or len(plan[i0][0]) != 3 or len(plan[i0][2]) != 1:
             continue
-        spec_idx = _groupsum_fragment(plan, i0, defs, uses, name_of, type_of, isdef)
+        spec_idx = _groupsum_fragment(plan, i0, defs, uses, name_of, type_of, isdef, star)
         if spec_idx is None:
             continue
         res, spec, idx = spec_idx
@@ -443,10 +526,54 @@ def fuse_select_groupsum(plan):
     return out
 
 
-def _groupsum_fragment(plan, i0, defs, uses, name_of, type_of, isdef):
+def _whole_gather(plan, d, name_of, isinput):
+    """Instruction d gathers a dimension column for every row of the fact table:
+    algebra.projection(V, D) or algebra.projectionpath(V, D) of plan inputs."""
+    a = plan[d][2]
+    return name_of(d) in ("algebra.projection", "algebra.projectionpath") and len(a) == 2 and isinput(a[0]) \
+        and isinput(a[1])
+
+
+def _groupsum_fragment(plan, i0, defs, uses, name_of, type_of, isdef, star=False):
     """(results, spec without "kept", instruction indices) of the fragment
-    around the group.group at i0, or None."""
+    around the group.group at i0, or None.  star: gathered columns too."""
     idx = {i0}
+    vias, inner_of = {}, {}
+    isinput = (lambda a: isinstance(a, str) and not isdef(a))
+
+    def gathered(v, cand):
+        """The route of v = D's values at the candidates cand through a join index, or None;
+        notes the projection underneath v so that it joins the fragment with v."""
+        if not star or not isdef(v):
+            return None
+        d = defs[v]
+        a = plan[d][2]
+        if name_of(d) == "algebra.projectionpath" and len(a) == 3 and a[0] == cand and isinput(a[1]) and isinput(a[2]):
+            via, dim = a[1], a[2]
+        elif name_of(d) == "algebra.projection" and len(a) == 2 and isdef(a[0]) and isinput(a[1]) \
+                and name_of(defs[a[0]]) == "algebra.projection" and len(plan[defs[a[0]]][2]) == 2 \
+                and plan[defs[a[0]]][2][0] == cand and isinput(plan[defs[a[0]]][2][1]):
+            via, dim = plan[defs[a[0]]][2][1], a[1]
+            inner_of[d] = defs[a[0]]
+        else:
+            return None
+        rid = "%s->%s" % (via, dim)
+        vias[rid] = (dim, via)
+        return rid
+
+    def gathered_pred(i):
+        """(the select, its route, c_{i-1}) where instruction i is c_i := algebra.projection(p, c_{i-1}) with p a
+        select without candidates on a column gathered from c_{i-1}; else None"""
+        a = plan[i][2]
+        if not star or name_of(i) != "algebra.projection" or len(a) != 2 or not isdef(a[0]) or not isinstance(a[1], str):
+            return None
+        pi = defs[a[0]]
+        if name_of(pi) not in SELECTS or len(plan[pi][0]) != 1:
+            return None
+        col, cand, rest = _select_split(name_of(pi), plan[pi][2])
+        rid = gathered(col, a[1]) if cand is None else None
+        return None if rid is None else (pi, rid, a[1])
+
     keyvars = [plan[i0][2][0]]
     g, e, h = plan[i0][0]
     # the refining subgroup: the only user of g1, with e1 and h1 unused
@@ -464,13 +591,20 @@ def _groupsum_fragment(plan, i0, defs, uses, name_of, type_of, isdef):
     if uses.get(h):
         return None
     # the keys: projections of one candidate list
-    if not all(isdef(k) and name_of(defs[k]) == "algebra.projection" for k in keyvars):
+    projs = ("algebra.projection", "algebra.projectionpath") if star else ("algebra.projection",)
+    if not all(isdef(k) and name_of(defs[k]) in projs for k in keyvars):
         return None
     ck = plan[defs[keyvars[0]]][2][0]
+    if star and name_of(defs[keyvars[0]]) == "algebra.projection" and isdef(ck) \
+            and name_of(defs[ck]) == "algebra.projection" and gathered_pred(defs[ck]) is None:
+        ck = plan[defs[ck]][2][0]        # a key gathered in two steps: the candidates under the join index
     if not isinstance(ck, str):
         return None
     # a fragment projection: algebra.projection(ck, column), the column a plan input
     def proj_col(v):
+        rid = gathered(v, ck)
+        if rid is not None:
+            return rid
         if not isdef(v) or name_of(defs[v]) != "algebra.projection":
             return None
         l, r = plan[defs[v]][2][:2]
@@ -566,11 +700,26 @@ def _groupsum_fragment(plan, i0, defs, uses, name_of, type_of, isdef):
         c = ck
         while True:
             i = defs[c]
+            gp = gathered_pred(i)
+            if gp is not None:
+                pi, rid, cand = gp
+                x = defs[plan[pi][2][0]]
+                chain.append((pi, rid))
+                idx.update((i, pi, x))
+                if not isdef(cand) or defs[cand] > i:
+                    s = cand             # a plan input: the first candidate list
+                    break
+                if set(uses.get(cand, [])) != {i, inner_of.get(x, x)}:
+                    return None
+                c = cand
+                continue
             if name_of(i) not in SELECTS or len(plan[i][0]) != 1:
                 return None
             col, cand, rest = _select_split(name_of(i), plan[i][2])
-            chain.append(i)
+            chain.append((i, None))
             if cand is None:
+                if star and isdef(col) and _whole_gather(plan, defs[col], name_of, isinput):
+                    return None          # a first select on a gathered column: left as written
                 break
             if not isdef(cand) or defs[cand] > i:
                 s = cand                 # a plan input: the first candidate list
@@ -581,10 +730,13 @@ def _groupsum_fragment(plan, i0, defs, uses, name_of, type_of, isdef):
         chain.reverse()
         if len(chain) > 4:
             return None
-        idx.update(chain)
+        idx.update(i for i, _ in chain)
     else:
         s = ck                           # no select: the groups of a plan's candidate list
     # nothing of the fragment but its results may be used outside it
+    idx.update(inner_of[i] for i in list(idx) if i in inner_of)
+    if len(vias) > 16:
+        return None
     inner = set()
     for i in idx:
         inner.update(plan[i][0])
@@ -592,7 +744,9 @@ def _groupsum_fragment(plan, i0, defs, uses, name_of, type_of, isdef):
         if any(u not in idx for u in uses.get(v, [])):
             return None
     spec = {"s": s, "preds": [], "keys": keys, "sums": sums, "outs": outs}
-    for i in chain:
+    for i, rid in chain:
         col, cand, rest = _select_split(name_of(i), plan[i][2])
-        spec["preds"].append((name_of(i), col, rest))
+        spec["preds"].append((name_of(i), col if rid is None else rid, rest))
+    if vias:
+        spec["vias"] = vias
     return tuple(res), spec, idx
