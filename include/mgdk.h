@@ -100,6 +100,14 @@ mgdk_BUN mgdk_set_colimg_min(mgdk_BUN rows);
  * changed since), -1 ineligible, 1 ready (then *width = 1 | 2 and *base = the
  * value of code 0; either may be NULL).  Never builds.  Tests. */
 int mgdk_colimg_info(const mgdk_bat *b, int *width, int64_t *base);
+/* The packed image of the same columns, a second and independent accelerator
+ * under the same policy: code = (value - base) / stride bit-packed in 4, 8,
+ * 12 or 16 bits per row (stride = the gcd of value - base), all ones for nil;
+ * a column whose codes do not fit 16 bits is ineligible.  The default fused
+ * Q6 reads its three predicate columns through it.  Same states as above
+ * (1: *wbits, *base and *stride are set; each may be NULL).  Never builds.
+ * Tests. */
+int mgdk_colpack_info(const mgdk_bat *b, int *wbits, int64_t *base, uint64_t *stride);
 const char *mgdk_GDKerrbuf(void);                /* gdk.h:1947 GDKerrbuf */
 void mgdk_GDKclrerr(void);
 int mgdk_sync(void);                             /* drain calling thread's stream */

@@ -91,12 +91,31 @@ struct Priv {
 	int64_t cimg_base;
 	BUN cimg_n;
 	const void *cimg_tail;
+	// the packed image (see ColPack): a second, independent accelerator of
+	// the same tails, code = (value - base) / stride bit-packed in 4 / 8 / 12
+	// / 16 bits per row (q6pack.h).  Built by colpack_get, same states, same
+	// lock and dropped wherever cimg is
+	Heap *pimg;
+	int pimg_state, pimg_wbits;
+	int64_t pimg_base;
+	uint64_t pimg_stride, pimg_maxc;
+	BUN pimg_n;
+	const void *pimg_tail;
 };
 // a column image: code = value - base in `width` bytes, all ones = nil
 struct ColImg {
 	const void *codes;
 	int width;               // 1 | 2
 	int64_t base;            // the column's smallest non-nil value
+};
+// a packed column image: code = (value - base) / stride in `wbits` bits,
+// all ones = nil, laid out as q6pack.h says
+struct ColPack {
+	const void *codes;
+	int wbits;               // 4 | 8 | 12 | 16
+	int64_t base;            // the column's smallest non-nil value
+	uint64_t stride;         // gcd of value - base over the non-nil values (1 when all are equal)
+	uint64_t maxcode;        // the column's largest code: (max - base) / stride
 };
 struct OidxSlot {
 	int refs;
@@ -128,6 +147,9 @@ void img8_drop(mgdk_bat *b);        // drops every accelerator of the tail (img8
 // b is ineligible, a view, too small, or the image cannot be allocated: the
 // caller then reads the tail itself
 bool colimg_get(mgdk_bat *b, ColImg *im);
+// b's packed image under the same policy and lock; false also when the codes
+// do not fit 16 bits
+bool colpack_get(mgdk_bat *b, ColPack *im);
 bool smap_get(const mgdk_bat *b, SelMap *m);
 void smap_set(mgdk_bat *b, Heap *h, const SelMap &m);   // takes a reference on h
 // b's order index (a reference on its heap, release with heap_decref; the

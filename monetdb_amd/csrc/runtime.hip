@@ -17,6 +17,7 @@
 #include <ctime>
 
 #include "mgdk_internal.h"
+#include "q6pack.h"
 
 namespace mgdk {
 
@@ -537,6 +538,11 @@ cimg_reset(Priv *p)
 	p->cimg_state = 0;
 	p->cimg_n = 0;
 	p->cimg_tail = nullptr;
+	heap_decref(p->pimg);
+	p->pimg = nullptr;
+	p->pimg_state = 0;
+	p->pimg_n = 0;
+	p->pimg_tail = nullptr;
 }
 
 void
@@ -1244,6 +1250,7 @@ mgdk_BBPunfix(mgdk_bat *b)
 		heap_decref(p->img8);
 		heap_decref(p->smap);
 		heap_decref(p->cimg);
+		heap_decref(p->pimg);
 		oidx_leave(p);
 		delete p;
 	}
@@ -1682,7 +1689,259 @@ cimg_encode(const void *tail, BUN n, int64_t base, uint64_t span, int w, void *o
 				   (unsigned long long) span, (uint16_t *) out, cell);
 }
 
+// ---- packed column images (Priv::pimg, q6pack.h) -----------------------------
+__device__ __forceinline__ unsigned long long
+pimg_gcd(unsigned long long a, unsigned long long b)
+{
+	while (b != 0) {
+		unsigned long long t;
+		if (((a | b) >> 32) == 0)
+			t = (unsigned) a % (unsigned) b;
+		else
+			t = a % b;
+		a = b;
+		b = t;
+	}
+	return a;
+}
+
+// *cell = gcd of v[i] - base over the non-nil values (starts at 0, the
+// neutral element; differences unsigned as in k_cimg_encode)
+template <typename T>
+__global__ __launch_bounds__(256) void
+k_pimg_gcd(const T *v, BUN n, long long base, unsigned long long *cell)
+{
+	const T nil = (T) ((T) 1 << (8 * sizeof(T) - 1));
+	unsigned long long g = 0;
+	for (BUN i = (BUN) blockIdx.x * blockDim.x + threadIdx.x; i < n && g != 1; i += (BUN) gridDim.x * blockDim.x) {
+		const T x = v[i];
+		if (x != nil)
+			g = pimg_gcd((unsigned long long) (long long) x - (unsigned long long) base, g);
+	}
+	for (int o = 32; o > 0; o >>= 1)
+		g = pimg_gcd(g, __shfl_xor(g, o));
+	if (__lane_id() == 0 && g != 0) {
+		unsigned long long old = *cell;
+		for (;;) {
+			const unsigned long long nw = pimg_gcd(old, g);
+			if (nw == old)
+				break;
+			const unsigned long long prev = atomicCAS(cell, old, nw);
+			if (prev == old)
+				break;
+			old = prev;
+		}
+	}
+}
+
+// one thread packs the 8 rows of a group (whole dwords, no byte shared with
+// another thread); rows from n on -- the padding to whole chunks -- get the
+// nil code.  cell[2] is set when a non-nil value lies outside [base, base +
+// span] or off the stride: the image is then thrown away
+template <typename T, int WB>
+__global__ __launch_bounds__(256) void
+k_pimg_encode(const T *v, BUN n, BUN ngroups, long long base, unsigned long long span, unsigned long long stride,
+	      uint32_t *out, long long *cell)
+{
+	const T nil = (T) ((T) 1 << (8 * sizeof(T) - 1));
+	const bool narrow = ((span | stride) >> 32) == 0;
+	bool bad = false;
+	for (BUN g = (BUN) blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (BUN) gridDim.x * blockDim.x) {
+		uint32_t c[Q6P_ROWS], w[WB / 4];
+#pragma unroll
+		for (unsigned k = 0; k < Q6P_ROWS; k++) {
+			const BUN r = g * Q6P_ROWS + k;
+			c[k] = q6p_nil(WB);
+			if (r >= n)
+				continue;
+			const T x = v[r];
+			if (x == nil)
+				continue;
+			const unsigned long long d = (unsigned long long) (long long) x - (unsigned long long) base;
+			if (d > span) {
+				bad = true;
+				continue;
+			}
+			const unsigned long long q = stride == 1 ? d : narrow ? (unsigned) d / (unsigned) stride : d / stride;
+			if (q * stride != d)
+				bad = true;
+			else
+				c[k] = (uint32_t) q;
+		}
+		q6p_pack8<WB>(c, w);
+		uint32_t *o = out + g * (WB / 4);
+#pragma unroll
+		for (int d = 0; d < WB / 4; d++)
+			o[d] = w[d];
+	}
+	if (bad)
+		cell[2] = 1;
+}
+
+template <typename T>
+static void
+pimg_encode(const void *tail, BUN n, int64_t base, uint64_t span, uint64_t stride, int wbits, void *out, long long *cell,
+	    hipStream_t st)
+{
+	const BUN ng = (n + Q6P_CH - 1) / Q6P_CH * (Q6P_CH / Q6P_ROWS);
+	const dim3 g(grid_for(ng, 256, 256 * 16)), blk(256);
+#define PENC(WB) hipLaunchKernelGGL((k_pimg_encode<T, WB>), g, blk, 0, st, (const T *) tail, n, ng, (long long) base, \
+				    (unsigned long long) span, (unsigned long long) stride, (uint32_t *) out, cell)
+	switch (wbits) {
+	case 4: PENC(4); break;
+	case 8: PENC(8); break;
+	case 12: PENC(12); break;
+	default: PENC(16); break;
+	}
+#undef PENC
+}
+
 namespace mgdk {
+// the smallest and largest non-nil value of b (n rows): from the positions
+// kept with the column (scan false; 0 when they are not known) or from a
+// pass over the tail (scan true; 0 when there is no non-nil value).  1: *lo
+// and *hi are set, -1: a HIP error
+static int
+col_extremes(const mgdk_bat *b, BUN n, bool scan, long long *cell, long long *h, hipStream_t st, int64_t *lo, int64_t *hi)
+{
+	const bool wide = b->twidth == 8;
+	const size_t w = wide ? 8 : 4;
+	if (!scan) {
+		if (!(b->tnonil && b->tminpos < n && b->tmaxpos < n))
+			return 0;
+		// the extremes are known: no min/max pass (the encode verifies them)
+		if (!hip_ok(hipMemcpyAsync(h, (const char *) b->theap + b->tminpos * w, w, hipMemcpyDeviceToHost, st), "memcpy") ||
+		    !hip_ok(hipMemcpyAsync(h + 1, (const char *) b->theap + b->tmaxpos * w, w, hipMemcpyDeviceToHost, st), "memcpy") ||
+		    !sync_data())
+			return -1;
+		int32_t l4, h4;
+		memcpy(&l4, h, 4);
+		memcpy(&h4, h + 1, 4);
+		*lo = wide ? h[0] : l4;
+		*hi = wide ? h[1] : h4;
+		return *lo <= *hi && (wide ? *lo != INT64_MIN : l4 != INT32_MIN) ? 1 : 0;
+	}
+	h[0] = INT64_MAX;
+	h[1] = INT64_MIN;
+	if (!hip_ok(hipMemcpyAsync(cell, h, 16, hipMemcpyHostToDevice, st), "memcpy"))
+		return -1;
+	const dim3 grid(grid_for(n, 1024, 256 * 16)), blk(256);
+	if (wide)
+		hipLaunchKernelGGL((k_cimg_minmax<int64_t>), grid, blk, 0, st, (const int64_t *) b->theap, n, cell);
+	else
+		hipLaunchKernelGGL((k_cimg_minmax<int32_t>), grid, blk, 0, st, (const int32_t *) b->theap, n, cell);
+	if (!hip_ok(hipMemcpyAsync(h, cell, 16, hipMemcpyDeviceToHost, st), "memcpy") || !sync_data())
+		return -1;
+	*lo = h[0];
+	*hi = h[1];
+	return *lo <= *hi ? 1 : 0;
+}
+
+bool
+colpack_get(mgdk_bat *b, ColPack *im)
+{
+	Priv *p = (Priv *) b->priv;
+	if (p == nullptr || p->view || b->theap == nullptr ||
+	    (b->ttype != MGDK_int && b->ttype != MGDK_date && b->ttype != MGDK_lng))
+		return false;
+	const BUN n = b->count;
+	// the lock of colimg_get, held in the same way
+	std::lock_guard<std::mutex> g(cimg_mu);
+	if (p->pimg_state != 0 && (p->pimg_n != n || p->pimg_tail != b->theap)) {
+		heap_decref(p->pimg);
+		p->pimg = nullptr;
+		p->pimg_state = 0;
+	}
+	if (p->pimg_state == 1) {
+		im->codes = p->pimg->base;
+		im->wbits = p->pimg_wbits;
+		im->base = p->pimg_base;
+		im->stride = p->pimg_stride;
+		im->maxcode = p->pimg_maxc;
+		return true;
+	}
+	const uint64_t thr = g_colimg_min.load(std::memory_order_relaxed);
+	if (p->pimg_state < 0 || thr == (uint64_t) MGDK_BUN_NONE || n == 0 || n < thr)
+		return false;
+
+	hipStream_t st = stream();
+	void *mb = meta_buf();
+	long long *h = (long long *) pinned(64);
+	if (mb == nullptr || h == nullptr)
+		return false;
+	long long *cell = (long long *) ((char *) mb + 2048);
+	const bool wide = b->twidth == 8;
+	auto ineligible = [&]() {
+		p->pimg_state = -1;
+		p->pimg_n = n;
+		p->pimg_tail = b->theap;
+		return false;
+	};
+	for (int pass = 0; pass < 2; pass++) {
+		int64_t lo = 0, hi = -1;
+		const int have = col_extremes(b, n, pass == 1, cell, h, st, &lo, &hi);
+		if (have < 0)
+			return false;
+		if (have == 0) {
+			if (pass == 1)
+				return ineligible();   // no non-nil value
+			continue;
+		}
+		const uint64_t span = (uint64_t) hi - (uint64_t) lo;
+		uint64_t stride = 1;
+		if (span > 14) {
+			// a narrower span gets 4 bits at stride 1 anyway
+			if (!hip_ok(hipMemsetAsync(cell + 3, 0, 8, st), "memset"))
+				return false;
+			const dim3 grid(grid_for(n, 1024, 256 * 16)), blk(256);
+			if (wide)
+				hipLaunchKernelGGL((k_pimg_gcd<int64_t>), grid, blk, 0, st, (const int64_t *) b->theap, n, (long long) lo,
+						   (unsigned long long *) cell + 3);
+			else
+				hipLaunchKernelGGL((k_pimg_gcd<int32_t>), grid, blk, 0, st, (const int32_t *) b->theap, n, (long long) lo,
+						   (unsigned long long *) cell + 3);
+			if (!hip_ok(hipMemcpyAsync(h + 3, cell + 3, 8, hipMemcpyDeviceToHost, st), "memcpy") || !sync_data())
+				return false;
+			stride = (uint64_t) h[3] ? (uint64_t) h[3] : 1;
+		}
+		const int wbits = q6p_width(span / stride);
+		if (wbits == 0)
+			return ineligible();
+		Heap *img = heap_new((size_t) q6p_bytes(n, wbits));
+		if (img == nullptr)
+			return false;              // stays unknown: the caller reads the tail
+		bool ok = hip_ok(hipMemsetAsync(cell + 2, 0, 8, st), "memset");
+		if (ok) {
+			if (wide)
+				pimg_encode<int64_t>(b->theap, n, lo, span, stride, wbits, img->base, cell, st);
+			else
+				pimg_encode<int32_t>(b->theap, n, lo, span, stride, wbits, img->base, cell, st);
+			ok = hip_ok(hipMemcpyAsync(h + 2, cell + 2, 8, hipMemcpyDeviceToHost, st), "memcpy") && sync_data();
+		}
+		if (ok && h[2] == 0) {
+			p->pimg = img;
+			p->pimg_wbits = wbits;
+			p->pimg_base = lo;
+			p->pimg_stride = stride;
+			p->pimg_maxc = span / stride;
+			p->pimg_n = n;
+			p->pimg_tail = b->theap;
+			p->pimg_state = 1;
+			im->codes = img->base;
+			im->wbits = wbits;
+			im->base = lo;
+			im->stride = stride;
+			im->maxcode = span / stride;
+			return true;
+		}
+		heap_decref(img);
+		if (!ok)
+			return false;
+		// the positions kept with the column did not hold its extremes: scan
+	}
+	return false;
+}
+
 bool
 colimg_get(mgdk_bat *b, ColImg *im)
 {
@@ -1717,45 +1976,21 @@ colimg_get(mgdk_bat *b, ColImg *im)
 		return false;
 	long long *cell = (long long *) ((char *) mb + 2048);
 	const bool wide = b->twidth == 8;
-	const size_t w = wide ? 8 : 4;
 	auto ineligible = [&]() {
 		p->cimg_state = -1;
 		p->cimg_n = n;
 		p->cimg_tail = b->theap;
 		return false;
 	};
-	int64_t lo = 0, hi = -1;
-	bool known = false;
-	if (b->tnonil && b->tminpos < n && b->tmaxpos < n) {
-		// the extremes are known: no min/max pass (the encode verifies them)
-		if (!hip_ok(hipMemcpyAsync(h, (const char *) b->theap + b->tminpos * w, w, hipMemcpyDeviceToHost, st), "memcpy") ||
-		    !hip_ok(hipMemcpyAsync(h + 1, (const char *) b->theap + b->tmaxpos * w, w, hipMemcpyDeviceToHost, st), "memcpy") ||
-		    !sync_data())
+	for (int pass = 0; pass < 2; pass++) {
+		int64_t lo = 0, hi = -1;
+		const int have = col_extremes(b, n, pass == 1, cell, h, st, &lo, &hi);
+		if (have < 0)
 			return false;
-		int32_t l4, h4;
-		memcpy(&l4, h, 4);
-		memcpy(&h4, h + 1, 4);
-		lo = wide ? h[0] : l4;
-		hi = wide ? h[1] : h4;
-		known = lo <= hi && (wide ? lo != INT64_MIN : l4 != INT32_MIN);
-	}
-	for (int pass = known ? 0 : 1; pass < 2; pass++) {
-		if (pass == 1) {
-			h[0] = INT64_MAX;
-			h[1] = INT64_MIN;
-			if (!hip_ok(hipMemcpyAsync(cell, h, 16, hipMemcpyHostToDevice, st), "memcpy"))
-				return false;
-			const dim3 grid(grid_for(n, 1024, 256 * 16)), blk(256);
-			if (wide)
-				hipLaunchKernelGGL((k_cimg_minmax<int64_t>), grid, blk, 0, st, (const int64_t *) b->theap, n, cell);
-			else
-				hipLaunchKernelGGL((k_cimg_minmax<int32_t>), grid, blk, 0, st, (const int32_t *) b->theap, n, cell);
-			if (!hip_ok(hipMemcpyAsync(h, cell, 16, hipMemcpyDeviceToHost, st), "memcpy") || !sync_data())
-				return false;
-			lo = h[0];
-			hi = h[1];
-			if (lo > hi)
+		if (have == 0) {
+			if (pass == 1)
 				return ineligible();   // no non-nil value
+			continue;
 		}
 		// max - min as an unsigned difference: exact over the whole lng range
 		const uint64_t span = (uint64_t) hi - (uint64_t) lo;
@@ -1816,4 +2051,24 @@ mgdk_colimg_info(const mgdk_bat *b, int *width, int64_t *base)
 			*base = p->cimg_base;
 	}
 	return p->cimg_state;
+}
+
+extern "C" int
+mgdk_colpack_info(const mgdk_bat *b, int *wbits, int64_t *base, uint64_t *stride)
+{
+	const Priv *p = b ? (const Priv *) b->priv : nullptr;
+	if (p == nullptr)
+		return 0;
+	std::lock_guard<std::mutex> g(cimg_mu);
+	if (p->pimg_state == 0 || p->pimg_n != b->count || p->pimg_tail != b->theap)
+		return 0;
+	if (p->pimg_state == 1) {
+		if (wbits)
+			*wbits = p->pimg_wbits;
+		if (base)
+			*base = p->pimg_base;
+		if (stride)
+			*stride = p->pimg_stride;
+	}
+	return p->pimg_state;
 }

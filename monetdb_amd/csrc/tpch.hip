@@ -31,6 +31,7 @@
 
 #include "mgdk_internal.h"
 #include "q6codes.h"
+#include "q6pack.h"
 
 using namespace mgdk;
 
@@ -159,6 +160,15 @@ struct Q6Args {
 	const void *simg;
 	uint32_t sclo, schi;       // sclo <= shipdate code <= schi
 	int sw;
+	// the packed variant (q6p::k_q6s): the packed images of shipdate, discount
+	// and quantity, their widths in bits (host side) and each predicate as
+	// pclo <= code <= pclo + pspan (an empty range: pclo above every code,
+	// pspan 0); discount = dbase + dstride * code
+	const void *pimg[3];
+	int pw[3];
+	uint32_t pclo[3], pspan[3];
+	uint64_t dstride;
+	int pcheap;                // every discount value lies in 0 .. 2^31 - 1
 };
 
 // one workgroup's exact revenue and (k_q6s) line count: written once per
@@ -884,6 +894,163 @@ k_q6s(Q6Args a)
 
 }  // namespace q6w
 
+// The cascade over packed images (variant 28): shipdate, discount and
+// quantity are read through their bit-packed images (Priv::pimg, q6pack.h:
+// SW / DW / QW bits per row), with q6w's row mapping -- a wave owns a 512-row
+// chunk, lane l its rows 8l .. 8l+7, which are WB bytes of an image.  At
+// these widths a 128-B line holds 64 to 256 rows, so guarding a predicate
+// column's load by the earlier predicates saves no line: the three are read
+// unconditionally and together (one load of 4 / 8 / 12 / 16 bytes per lane
+// each), and the next chunk's three loads are issued behind this chunk's
+// price loads.  extendedprice is read as in q6w (one 16-byte load per row
+// pair still in), so the price lines fetched are variant 26's.  The products
+// are taken in a per-lane loop over the rows still in -- the wave runs it as
+// often as its fullest lane has rows, usually once or twice at Q6's
+// selectivity -- instead of one guarded 128-bit block per row slot.
+namespace q6p {
+
+constexpr unsigned CH = Q6P_CH;
+constexpr uint64_t NOCHUNK = ~(uint64_t) 0;
+
+// the lane's 8 codes of a chunk (WB / 4 dwords): never guarded, nontemporal
+template <int WB>
+__device__ __forceinline__ void
+ldcodes(const void *img, uint64_t chunk, unsigned lane, uint32_t *w)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__) && !defined(__gfx942__)
+#error "q6p::ldcodes: buffer descriptor word 3 is laid out for gfx942 / gfx950 only"
+#endif
+	typedef unsigned int u3 __attribute__((ext_vector_type(3)));
+	constexpr unsigned CB = CH / 8 * WB;      // bytes of a chunk
+	constexpr int NT = 2;                     // the nt bit of the cache policy
+	__amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *) ((const char *) img + chunk * CB), (short) 0, CB,
+								      0x00020000);
+	const unsigned off = (unsigned) WB * lane;
+	if constexpr (WB == 4) {
+		w[0] = __builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, NT);
+	} else if constexpr (WB == 8) {
+		const q6w::u2 v = __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, NT);
+		w[0] = v.x;
+		w[1] = v.y;
+	} else if constexpr (WB == 12) {
+		const u3 v = __builtin_amdgcn_raw_buffer_load_b96(rs, off, 0, NT);
+		w[0] = v.x;
+		w[1] = v.y;
+		w[2] = v.z;
+	} else {
+		const q6u4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, NT);
+		w[0] = v.x;
+		w[1] = v.y;
+		w[2] = v.z;
+		w[3] = v.w;
+	}
+}
+
+// code k of the lane's dwords for a k that differs from lane to lane
+template <int WB>
+__device__ __forceinline__ uint32_t
+code_at(const uint32_t *w, uint32_t k)
+{
+	if constexpr (WB == 4) {
+		return (w[0] >> (4 * k)) & 0xfu;
+	} else if constexpr (WB == 8) {
+		return (((k & 4) ? w[1] : w[0]) >> (8 * (k & 3))) & 0xffu;
+	} else if constexpr (WB == 16) {
+		const uint32_t x = (k & 4) ? ((k & 2) ? w[3] : w[2]) : ((k & 2) ? w[1] : w[0]);
+		return (x >> (16 * (k & 1))) & 0xffffu;
+	} else {
+		const uint32_t bit = 12 * k, d = bit >> 5;
+		const uint32_t lo = d == 0 ? w[0] : d == 1 ? w[1] : w[2];
+		const uint32_t hi = d == 0 ? w[1] : d == 1 ? w[2] : 0u;
+		return (uint32_t) ((((uint64_t) hi << 32) | lo) >> (bit & 31)) & 0xfffu;
+	}
+}
+
+// one chunk: its codes are in ps / pd / pq already; those of chunk cn (if
+// any) are loaded into them behind the price loads
+template <int SW, int DW, int QW>
+__device__ __forceinline__ void
+chunk(const Q6Args &a, uint64_t c, unsigned lane, hge &acc, uint32_t &nlines, uint32_t *ps, uint32_t *pd, uint32_t *pq,
+      uint64_t cn)
+{
+	// pclo <= code <= pclo + pspan as one unsigned compare (an empty range
+	// comes as pclo above every code); row by row, so that each row's three
+	// compares meet as wave masks in scalar registers before they become a
+	// bit of m
+	uint32_t m = 0;
+#pragma unroll
+	for (int k = 0; k < 8; k++) {
+		const bool oks = q6p_code<SW>(ps, k) - a.pclo[0] <= a.pspan[0];
+		const bool okd = q6p_code<DW>(pd, k) - a.pclo[1] <= a.pspan[1];
+		const bool okq = q6p_code<QW>(pq, k) - a.pclo[2] <= a.pspan[2];
+		m |= (uint32_t) (oks & okd & okq) << k;    // & not &&: no branch per row
+	}
+	uint32_t dcw[DW / 4];
+#pragma unroll
+	for (int i = 0; i < DW / 4; i++)
+		dcw[i] = pd[i];
+	// extendedprice where all three hold
+	long long v[8];
+	nlines += q6w::lines<0>(__ballot(m != 0));
+	q6w::ldraw(a.price, c, lane, m, v);
+	if (cn != NOCHUNK) {
+		ldcodes<SW>(a.pimg[0], cn, lane, ps);
+		ldcodes<DW>(a.pimg[1], cn, lane, pd);
+		ldcodes<QW>(a.pimg[2], cn, lane, pq);
+	}
+	// the products of the rows still in, one per lane and pass
+	while (m != 0) {
+		const uint32_t k = (uint32_t) __builtin_ctz(m);
+		m &= m - 1;
+		const bool b0 = k & 1, b1 = k & 2, b2 = k & 4;
+		const long long t0 = b0 ? v[1] : v[0], t1 = b0 ? v[3] : v[2], t2 = b0 ? v[5] : v[4], t3 = b0 ? v[7] : v[6];
+		const long long u0 = b1 ? t1 : t0, u1 = b1 ? t3 : t2;
+		const long long p = b2 ? u1 : u0;
+		const uint32_t dc = code_at<DW>(dcw, k);
+		if (p == INT64_MIN)
+			continue;
+		if (a.pcheap) {
+			// 0 <= discount < 2^31: signed 64 x unsigned 32 in two 32-bit multiply-adds
+			const uint32_t d = (uint32_t) a.dbase + (uint32_t) a.dstride * dc;
+			const uint64_t lo = (uint64_t) (uint32_t) p * d;
+			const int64_t hi = (int64_t) (int32_t) (p >> 32) * (int64_t) (int32_t) d + (int64_t) (lo >> 32);
+			acc += (hge) (((uhge) (hge) hi << 32) | (uint32_t) lo);
+		} else {
+			const int64_t di = (int64_t) ((uint64_t) a.dbase + a.dstride * (uint64_t) dc);
+			acc += (hge) p * (hge) di;
+		}
+	}
+}
+
+template <int SW, int DW, int QW>
+__global__ __launch_bounds__(256) void
+k_q6s(Q6Args a)
+{
+	hge acc = 0;
+	uint32_t nlines = 0;
+	const unsigned lane = __lane_id();
+	const uint64_t nch = a.n / CH;
+	const uint64_t nw = (uint64_t) gridDim.x * (blockDim.x / 64);
+	// wave-uniform for the compiler, as in k_q6s above
+	uint64_t c = (uint64_t) blockIdx.x * (blockDim.x / 64) + (unsigned) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
+	uint32_t ps[SW / 4], pd[DW / 4], pq[QW / 4];
+	if (c < nch) {
+		ldcodes<SW>(a.pimg[0], c, lane, ps);
+		ldcodes<DW>(a.pimg[1], c, lane, pd);
+		ldcodes<QW>(a.pimg[2], c, lane, pq);
+	}
+	for (; c < nch; c += nw)
+		chunk<SW, DW, QW>(a, c, lane, acc, nlines, ps, pd, pq, c + nw < nch ? c + nw : NOCHUNK);
+	// the rows past the last full chunk, from the raw columns
+	if (blockIdx.x == 0) {
+		for (uint64_t r = nch * CH + threadIdx.x; r < a.n; r += blockDim.x)
+			acc += q6_row(a, a.sd[r], a.disc[r], a.qty[r], a.price[r]);
+	}
+	q6_publish(a, acc, nlines);
+}
+
+}  // namespace q6p
+
 __global__ __launch_bounds__(256) void
 k_q6_scalar(Q6Args a)
 {
@@ -1398,7 +1565,7 @@ mgdk_tpch_lineitem(uint64_t seed, uint64_t row0, uint64_t n, uint64_t sf_parts, 
 // instead of 10.53; variant 24 at 32 / 64 / 128 WG/CU 1.014 / 0.990 / 1.003 ms,
 // variant 25 1.012 / 1.002 / 1.094 ms, variant 19 at 128 WG/CU 1.645 ms on
 // the same box -- hence 24 at 64 WG/CU.
-// variants 26 / 27 (the default: 26): the same cascade with the wide
+// variants 26 / 27 (the default before 28: 26): the same cascade with the wide
 // row-to-lane mapping (q6w::k_q6s: 512-row chunks, 8 rows per lane; 26 one
 // chunk at a time with the next chunk's shipdates prefetched, 27 two chunks
 // in flight) and shipdate read through its image as well -- 2 bytes per row
@@ -1409,8 +1576,16 @@ mgdk_tpch_lineitem(uint64_t seed, uint64_t row0, uint64_t n, uint64_t sf_parts, 
 // 0.690 / 0.688 / 0.688 ms at 32 / 64 / 96 WG/CU (a second chunk of
 // prefetch distance: 0.689), two chunks in flight 0.709 / 0.702 / 0.709 ms
 // -- hence 26 at 64 WG/CU.
-constexpr int Q6_IMG_VARIANT = 24, Q6_WIDE_VARIANT = 26;
-static std::atomic<int> q6_variant{Q6_WIDE_VARIANT}, q6_bpc{64};
+// variant 28: q6p::k_q6s, the three predicate columns read unconditionally
+// through their packed images (4 / 8 / 12 / 16 bits per row: 12 + 4 + 8 bits
+// = 3.0 B/row for the generated lineitem where variant 26's images take 5),
+// extendedprice as in variant 26, the products in a loop over the rows still
+// in.  mgdk_q6_fused asks for the packed images (colpack_get) and not for
+// the byte images; a column without a packed image makes the call variant
+// 26's, byte images included.  Variants up to 27 never ask for a packed
+// image.  profiles/q6_packed/ has the measurements.
+constexpr int Q6_IMG_VARIANT = 24, Q6_WIDE_VARIANT = 26, Q6_PACK_VARIANT = 28;
+static std::atomic<int> q6_variant{Q6_PACK_VARIANT}, q6_bpc{64};
 static thread_local unsigned long long q6_lines = 0, q6_bytes = 0;
 // fused Q1 main pass (tools/q1_tune.py, profiles/r01/q1_tune.log)
 static std::atomic<int> q1_layout{MGDK_Q1_LAYOUT}, q1_blocks{MGDK_Q1_BLOCKS};
@@ -1423,11 +1598,32 @@ launch_q6(Q6Args a, int variant, int bpc, hipStream_t st)
 	if (variant >= 16 || v7 >= 3) {            // k_q6c / k_q6s: per-workgroup partials
 		const uint32_t nb = 256u * (unsigned) bpc;
 		a.parts = (Q6Part *) scratch((size_t) nb * sizeof(Q6Part));
-		if (a.parts == nullptr)
-			return false;
 	}
+	// k_q6_fin writes all three words of out; every other end starts from zeros
+	if (a.parts == nullptr && !hip_ok(hipMemsetAsync(a.out, 0, 128, st), "memset"))
+		return false;
+	if ((variant >= 16 || v7 >= 3) && a.parts == nullptr)
+		return false;
 	if (variant >= 16) {                 // predicate cascade (k_q6s)
 		dim3 g(256u * (unsigned) bpc), blk(256);
+		if (variant >= Q6_PACK_VARIANT && a.pimg[0] != nullptr) {
+#define Q6P(S, D, Q) hipLaunchKernelGGL((q6p::k_q6s<S, D, Q>), g, blk, 0, st, a)
+#define Q6PQ(S, D) do { switch (a.pw[2]) { case 4: Q6P(S, D, 4); break; case 8: Q6P(S, D, 8); break; \
+			case 12: Q6P(S, D, 12); break; default: Q6P(S, D, 16); break; } } while (0)
+#define Q6PD(S) do { switch (a.pw[1]) { case 4: Q6PQ(S, 4); break; case 8: Q6PQ(S, 8); break; \
+			case 12: Q6PQ(S, 12); break; default: Q6PQ(S, 16); break; } } while (0)
+			switch (a.pw[0]) {
+			case 4: Q6PD(4); break;
+			case 8: Q6PD(8); break;
+			case 12: Q6PD(12); break;
+			default: Q6PD(16); break;
+			}
+#undef Q6PD
+#undef Q6PQ
+#undef Q6P
+			hipLaunchKernelGGL(k_q6_fin, dim3(1), dim3(1024), 0, st, a.parts, g.x, a.out);
+			return true;
+		}
 		const void *zbuf = zero_region();
 		if (zbuf == nullptr) {
 			variant = 14;
@@ -1548,9 +1744,44 @@ mgdk_q6_fused(mgdk_bat *shipdate, mgdk_bat *discount, mgdk_bat *quantity, mgdk_b
 	a.dw = a.qw = a.sw = 0;
 	a.dbase = 0;
 	a.dclo = a.dchi = a.qk = a.sclo = a.schi = 0;
-	const int variant = q6_variant.load();
+	a.pimg[0] = a.pimg[1] = a.pimg[2] = nullptr;
+	a.dstride = 1;
+	a.pcheap = 0;
+	int variant = q6_variant.load();
 	const bool al = aligned16(a.sd) && aligned16(a.disc) && aligned16(a.qty) && aligned16(a.price);
-	if (variant >= Q6_IMG_VARIANT && al && a.n) {
+	if (variant >= Q6_PACK_VARIANT && al && a.n) {
+		// the packed images of the three predicate columns (built here on
+		// their first use); without all three the call is variant 26's
+		mgdk_bat *pc[3] = {shipdate, discount, quantity};
+		ColPack pk[3];
+		bool all = true;
+		for (int i = 0; i < 3 && all; i++)
+			all = colpack_get(pc[i], &pk[i]);
+		if (all) {
+			uint32_t clo[3], chi[3];
+			// sd >= d0 && sd < d1 as a code range over [d0, d1 - 1] (in 64
+			// bits: d1 may be the smallest int); quantity < qmax as [0, k - 1]
+			q6_pcode_range(pk[0].base, pk[0].stride, pk[0].wbits, d0, (int64_t) d1 - 1, &clo[0], &chi[0]);
+			q6_pcode_range(pk[1].base, pk[1].stride, pk[1].wbits, dlo, dhi, &clo[1], &chi[1]);
+			clo[2] = 0;
+			chi[2] = q6_pcode_below(pk[2].base, pk[2].stride, pk[2].wbits, qmax);
+			if (chi[2]-- == 0)
+				clo[2] = 1, chi[2] = 0;
+			for (int i = 0; i < 3; i++) {
+				a.pimg[i] = pk[i].codes;
+				a.pw[i] = pk[i].wbits;
+				q6_pcode_window(clo[i], chi[i], &a.pclo[i], &a.pspan[i]);
+			}
+			a.dbase = pk[1].base;
+			a.dstride = pk[1].stride;
+			// the column's largest discount, in 128 bits
+			const __int128 dmaxv = (__int128) pk[1].base + (__int128) pk[1].stride * pk[1].maxcode;
+			a.pcheap = pk[1].base >= 0 && dmaxv < ((__int128) 1 << 31);
+		} else {
+			variant = Q6_WIDE_VARIANT;
+		}
+	}
+	if (variant >= Q6_IMG_VARIANT && al && a.n && a.pimg[0] == nullptr) {
 		// the images of discount and quantity (built here on their first
 		// use); without one the kernel reads that column raw
 		ColImg im;
@@ -1576,8 +1807,10 @@ mgdk_q6_fused(mgdk_bat *shipdate, mgdk_bat *discount, mgdk_bat *quantity, mgdk_b
 	a.out = (unsigned long long *) meta_buf();
 	hipStream_t st = stream();
 	bool cascade = false;
-	// out: [0..1] revenue, [2] column lines read by the cascade
-	if (!hip_ok(hipMemsetAsync(a.out, 0, 128, st), "memset"))
+	// out: [0..1] revenue, [2] column lines read by the cascade.  Zeroed here
+	// for an empty input and the scalar kernel; launch_q6 zeroes it for the
+	// kernels that add into it and not for those that end in k_q6_fin
+	if (!(a.n && al) && !hip_ok(hipMemsetAsync(a.out, 0, 128, st), "memset"))
 		return -1;
 	{
 		ProfScope prof("q6_fused");
@@ -1593,7 +1826,10 @@ mgdk_q6_fused(mgdk_bat *shipdate, mgdk_bat *discount, mgdk_bat *quantity, mgdk_b
 		return -1;
 	memcpy(revenue, h, 16);
 	q6_lines = h[2];
-	q6_bytes = cascade ? a.n * (uint64_t) (a.simg ? a.sw : 4) + 128 * h[2] : a.n * 28;
+	if (cascade && a.pimg[0])
+		q6_bytes = a.n * (uint64_t) (a.pw[0] + a.pw[1] + a.pw[2]) / 8 + 128 * h[2];
+	else
+		q6_bytes = cascade ? a.n * (uint64_t) (a.simg ? a.sw : 4) + 128 * h[2] : a.n * 28;
 	return 0;
 }
 

@@ -215,6 +215,7 @@ _SIGS = {
     "mgdk_set_fp_parallel_min": (C.c_uint64, [C.c_uint64]),
     "mgdk_set_colimg_min": (C.c_uint64, [C.c_uint64]),
     "mgdk_colimg_info": (C.c_int, [P, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "mgdk_colpack_info": (C.c_int, [P, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]),
     "mgdk_BATcalcavg": (C.c_int, [P, P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]),
     "mgdk_BATcheckorderidx": (C.c_bool, [P]),
     "mgdk_OIDXdestroy": (None, [P]),
@@ -825,6 +826,15 @@ def colimg_info(b):
     return (st, int(w.value), int(base.value)) if st == 1 else (st, None, None)
 
 
+def colpack_info(b):
+    """State of b's packed image (code = (value - base) / stride in wbits = 4 / 8 / 12 / 16
+    bits per row): (0, None, None, None) unknown, (-1, None, None, None) ineligible,
+    (1, wbits, base, stride) ready.  Never builds one."""
+    w, base, stride = C.c_int(0), C.c_int64(0), C.c_uint64(0)
+    st = int(lib().mgdk_colpack_info(b.ptr, C.byref(w), C.byref(base), C.byref(stride)))
+    return (st, int(w.value), int(base.value), int(stride.value)) if st == 1 else (st, None, None, None)
+
+
 def BATorderidx(b, stable=False):
     """BATorderidx (gdk_orderidx.c:184): keep b's sort order with b"""
     _chk(lib().mgdk_BATorderidx(b.ptr, stable))
@@ -1428,9 +1438,13 @@ def q6_set_variant(variant, blocks_per_cu):
     quantity through their column images where they have one (256-row chunks, 2 / 4 in
     flight), 26 / 27 = the cascade over 512-row chunks with 8 rows per lane, reading shipdate
     through its column image as well (26: one chunk at a time with the next chunk's shipdates
-    prefetched, 27: 2 chunks in flight; the default is 26 at 64 workgroups per CU; see
-    set_colimg_min).  Variants below 24 never use images, variants below 26 never ask for a
-    shipdate image."""
+    prefetched, 27: 2 chunks in flight), 28 = the three predicate columns read whole through
+    their packed images (4 / 8 / 12 / 16 bits per row, colpack_info) with the next chunk's
+    codes prefetched, extendedprice as in 26 and the products in a loop over the passing
+    rows; a column without a packed image makes the call 26's.  The default is 28 at 64
+    workgroups per CU; see set_colimg_min.  Variants below 24 never use images, variants
+    below 26 never ask for a shipdate image, variants below 28 never ask for a packed
+    image."""
     lib().mgdk_q6_set_variant(C.c_int(variant), C.c_int(blocks_per_cu))
 
 

@@ -10,7 +10,7 @@ from monetdb_amd import gdk
 gdk.init(0)
 rows = int(os.environ.get("Q6_ROWS", "600121500"))
 mk = lambda y, m, d: (((y + 4712) * 12 + m - 1) << 5) | d
-variants = [int(x) for x in sys.argv[1].split(",")] if len(sys.argv) > 1 else [26, 24, 19]
+variants = [int(x) for x in sys.argv[1].split(",")] if len(sys.argv) > 1 else [28, 26, 24, 19]
 # every kernel of every variant, image builds included, runs once on small
 # columns first: the first calls timed below pay no code loading
 for variant in variants:
@@ -31,7 +31,9 @@ for variant in variants:
         rev = gdk.q6_fused(*args)
         ms.append((time.perf_counter() - t) * 1e3)
     images = [gdk.colimg_info(cols[k])[:2] for k in ("shipdate", "discount", "quantity")]
-    print("variant %d: first call %.3f ms, next calls %s ms, images (state, width) %s, revenue %d, bytes %d" % (
-        variant, ms[0], " ".join("%.3f" % x for x in ms[1:]), images, rev, gdk.q6_last_bytes()))
+    packs = [gdk.colpack_info(cols[k]) for k in ("shipdate", "discount", "quantity")]
+    print("variant %d: first call %.3f ms, next calls %s ms, images (state, width) %s, packed images "
+          "(state, bits, base, stride) %s, revenue %d, bytes %d" % (
+              variant, ms[0], " ".join("%.3f" % x for x in ms[1:]), images, packs, rev, gdk.q6_last_bytes()))
     del cols, args
     gdk.lib().mgdk_mem_release_cache()

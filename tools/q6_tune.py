@@ -17,8 +17,10 @@ args = (cols["shipdate"], cols["discount"], cols["quantity"], cols["extendedpric
 L = gdk.lib()
 L.mgdk_q6_set_variant.argtypes = [C.c_int, C.c_int]
 ref = gdk.q6_fused(*args)
-vs = [int(x) for x in sys.argv[1].split(",")] if len(sys.argv) > 1 else [0, 1, 2, 3, 4, 5, 9, 12]
-bs = [int(x) for x in sys.argv[2].split(",")] if len(sys.argv) > 2 else [4, 8, 16]
+# default: the image cascades (24: byte images of discount and quantity, 26 / 27: of shipdate
+# too, 28: packed images) over the workgroups per CU they were tuned at
+vs = [int(x) for x in sys.argv[1].split(",")] if len(sys.argv) > 1 else [24, 26, 27, 28]
+bs = [int(x) for x in sys.argv[2].split(",")] if len(sys.argv) > 2 else [32, 64, 96, 128]
 variants = [(v, b) for v in vs for b in bs]
 res = {k: [] for k in variants}
 gdk.prof_enable(True)
